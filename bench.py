@@ -16,6 +16,18 @@ is the whole-job achieved req/s aggregated over all ranks (max rank
 time). ``--mode wave`` keeps the round-1 closed-loop wave benchmark for
 comparability.
 
+A plain run does only what the headline figure needs: engine setup, the
+warmup waves, the timed steps, the result line. ``--dump-outputs DIR``
+additionally writes what the last timed step returned to its callers
+(``DIR/out_ids.npy``: the generated token ids of rank 0's last cohort,
+float32 [batch, gen_tokens], rows in prompt order). Prompts and weights
+are seeded, so two builds run with the same arguments see the same
+inputs; the open-loop mode schedules arrivals against the engine's own
+decode-step count (see run_open_loop) and a wave arrives all at once, so
+the batching and the tokens repeat from run to run; the wall clock only
+paces and times the run. ``--full`` is reserved for
+secondary measurements that take runs of their own; today there are none.
+
 Launch (the driver does this for N>1):
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
@@ -31,6 +43,7 @@ import statistics
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -67,7 +80,41 @@ def parse_args():
         "offers exactly the achieved open-loop capacity, so the timed "
         "region is saturated with a bounded queue (stable TTFT)",
     )
-    return p.parse_args()
+    p.add_argument(
+        "--dump-outputs", metavar="DIR", default=None,
+        help="after the timed steps, write the token ids the last timed "
+        "step generated (rank 0) to DIR/out_ids.npy as float32 "
+        "[batch, gen_tokens]",
+    )
+    p.add_argument(
+        "--full", action="store_true",
+        help="also run the secondary measurements that need runs of their "
+        "own (none at present: a plain run already does only what the "
+        "headline figure needs)",
+    )
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(path: str, reqs, gen_tokens: int) -> None:
+    """Write the cohort's generated token ids as float32 [rows, gen_tokens]
+    (ids are far below 2**24, so float32 holds them exactly). A cohort too
+    large for DUMP_MAX_BYTES is cut to a fixed, seeded sample of its rows."""
+    # a preempted request carries its earlier tokens at its prompt's tail
+    out = np.asarray(
+        [(r.prompt_ids + r.out_ids)[-gen_tokens:] for r in reqs], dtype=np.float32
+    )
+    max_rows = max(1, DUMP_MAX_BYTES // (gen_tokens * 4))
+    if out.shape[0] > max_rows:
+        rows = np.random.default_rng(0).choice(out.shape[0], max_rows, replace=False)
+        out = out[np.sort(rows)]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "out_ids.npy"), out)
 
 
 def make_prompts(batch: int, prompt_len: int, vocab: int, seed: int):
@@ -76,7 +123,8 @@ def make_prompts(batch: int, prompt_len: int, vocab: int, seed: int):
     return [t.tolist() for t in toks]
 
 
-def run_wave(engine: LLMEngine, prompts, gen_tokens: int, sp: dict = {}):
+def run_wave(engine: LLMEngine, prompts, gen_tokens: int, sp: dict = {}, keep=None):
+    """One closed-loop wave; the requests are appended to `keep` if given."""
     t0 = time.monotonic()
     reqs = [
         EngineRequest(p, SamplingParams(max_tokens=gen_tokens, ignore_eos=True, **sp))
@@ -93,38 +141,63 @@ def run_wave(engine: LLMEngine, prompts, gen_tokens: int, sp: dict = {}):
     ]
     assert all(r.state == "finished" for r in reqs)
     assert all(len(r.out_ids) == gen_tokens for r in reqs)
+    if keep is not None:
+        keep.extend(reqs)
     return ttfts
 
 
+LOAD = 0.95  # open-loop arrivals per decode step, as a share of batch/gen_tokens
+
+
 def run_open_loop(engine: LLMEngine, prompts, gen_tokens: int, qps: float, seed: int,
-                  sp: dict = {}):
+                  batch: int, sp: dict = {}, keep=None):
     """Drive len(prompts) requests as a Poisson process at `qps` req/s.
 
-    Returns (ttfts_ms, elapsed_s). TTFT is measured from each request's
+    Returns (ttfts_ms, elapsed_s); the requests, in prompt order, are
+    appended to `keep` if given. TTFT is measured from each request's
     scheduled arrival time; requests arriving while the engine is busy
-    queue exactly as gateway traffic would."""
+    queue exactly as gateway traffic would.
+
+    The arrival clock is the engine's own decode-step count, not the wall
+    clock, so which requests share a forward pass, and with it every
+    generated token, repeats from run to run: one decode step advances
+    the clock by LOAD * batch / gen_tokens arrivals (a full batch turns
+    over every gen_tokens steps, so the running set sits at LOAD of the
+    batch), and no step starts before its clock reading divided by `qps`
+    has passed on the wall clock (once every request has arrived, the
+rest drains unpaced). An engine that keeps up therefore
+    serves exactly the offered rate; one that does not is saturated and
+    the achieved rate is its capacity."""
     rng = random.Random(seed)
-    t = 0.0
-    arrivals = []
+    u = 0.0
+    units = []  # arrival times of a unit-rate Poisson process
     for _ in prompts:
-        arrivals.append(t)
-        t += rng.expovariate(qps)
+        units.append(u)
+        u += rng.expovariate(1.0)
+    arrivals = [u / qps for u in units]
+    per_step = LOAD * batch / gen_tokens
     reqs = [
         EngineRequest(p, SamplingParams(max_tokens=gen_tokens, ignore_eos=True, **sp))
         for p in prompts
     ]
+    d0 = engine.stats["decode_steps"]
+    idle = 0.0  # clock time skipped while the engine had nothing to do
     t0 = time.monotonic()
     nxt = 0
     n = len(reqs)
     while True:
-        now = time.monotonic() - t0
-        while nxt < n and arrivals[nxt] <= now:
+        clock = (engine.stats["decode_steps"] - d0) * per_step + idle
+        while nxt < n and units[nxt] <= clock:
             engine.add_request(reqs[nxt])
             nxt += 1
         if engine.has_work():
+            # pace only while arrivals remain: the tail drains flat out
+            ahead = clock / qps - (time.monotonic() - t0) if nxt < n else 0.0
+            if ahead > 0:
+                time.sleep(ahead)
             engine.step()
         elif nxt < n:
-            time.sleep(min(0.002, max(0.0, arrivals[nxt] - (time.monotonic() - t0))))
+            idle += units[nxt] - clock
         else:
             break
     if engine.device.type == "cuda":
@@ -136,6 +209,8 @@ def run_open_loop(engine: LLMEngine, prompts, gen_tokens: int, qps: float, seed:
         if r.first_token_time
     ]
     assert all(r.state == "finished" for r in reqs)
+    if keep is not None:
+        keep.extend(reqs)
     return ttfts, elapsed
 
 
@@ -169,6 +244,9 @@ def main():
         max_model_len=args.prompt_len + args.gen_tokens + 8,
         seed=1234 + rank,
         kv_dtype=args.kv_dtype,
+        # the engine holds a trickle of arrivals back by wall-clock age;
+        # the open-loop run admits at once so that its batching repeats
+        admit_min_batch=1 if args.mode == "qps" else None,
     )
     vocab = engine.full_config.vocab_size
 
@@ -213,6 +291,7 @@ def main():
     barrier_sync()
     t_start = time.monotonic()
     ttfts = []
+    timed_reqs = []  # every timed request in prompt order (references only)
     if args.mode == "qps":
         prompts = []
         for s in range(args.steps):
@@ -220,13 +299,14 @@ def main():
                 args.batch, args.prompt_len, vocab, 2000 + s + rank * 7919
             )
         ttfts, _ = run_open_loop(
-            engine, prompts, args.gen_tokens, qps, seed=97 + rank, sp=sp
+            engine, prompts, args.gen_tokens, qps, seed=97 + rank,
+            batch=args.batch, sp=sp, keep=timed_reqs,
         )
     else:
         for s in range(args.steps):
             ttfts += run_wave(
                 engine, make_prompts(args.batch, args.prompt_len, vocab, 2000 + s + rank * 7919),
-                args.gen_tokens, sp,
+                args.gen_tokens, sp, keep=timed_reqs,
             )
     barrier_sync()
     elapsed = time.monotonic() - t_start
@@ -238,6 +318,10 @@ def main():
             t = t.to(engine.device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if rank == 0 and args.dump_outputs:
+        # the last step is the last batch-sized cohort of arrivals
+        dump_outputs(args.dump_outputs, timed_reqs[-args.batch:], args.gen_tokens)
 
     if rank == 0:
         total_reqs = args.batch * args.steps * world_size

@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,6 +56,25 @@ def test_wave_mode():
     d = run_bench(["--mode", "wave"])
     check_schema(d, "req/sec")
     assert d["config"]["mode"] == "closed-loop-waves"
+
+
+def test_dump_outputs_last_step_repeats(tmp_path):
+    """--dump-outputs writes the last timed step's token ids; the inputs
+    and the arrival schedule are seeded, so a second run (here with --full,
+    which adds nothing to the timed path) reproduces them exactly."""
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = run_bench(
+            ["--steps", "3", "--dump-outputs", str(tmp_path / name)] + extra
+        )
+        check_schema(d, "req/sec @ fixed QPS")
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert [p.name for p in (tmp_path / name).iterdir()] == ["out_ids.npy"]
+        dumps.append(np.load(tmp_path / name / "out_ids.npy"))
+    a, b = dumps
+    assert a.dtype == np.float32 and a.shape == (8, 6)  # [batch, gen_tokens]
+    assert (a == np.round(a)).all() and (a >= 0).all() and (a < 512).all()
+    assert (a == b).all()
 
 
 @pytest.mark.timeout(420)

@@ -1,3 +1,5 @@
+from pathlib import Path
+
 import pytest
 
 from llmapigateway_amd.config import jsonc
@@ -48,10 +50,12 @@ def test_bytes_input():
 
 
 def test_reference_example_configs_parse():
-    # the real reference example files use comments + nesting; our parser must accept them
+    # the real reference example files use comments + nesting; our parser must
+    # accept them (verbatim copies are kept as fixtures under tests/golden/)
+    golden = Path(__file__).resolve().parent / "golden"
     for p in (
-        "/root/reference/providers.json.example",
-        "/root/reference/models_fallback_rules.json.example",
+        golden / "reference_providers.json.example",
+        golden / "reference_models_fallback_rules.json.example",
     ):
         with open(p) as f:
             data = jsonc.load(f)
