@@ -9,11 +9,17 @@ flat varlen batch (ForwardBatch) in one of two modes:
 - decode: one token per running sequence; ops.attention_decode over the
   paged cache via block tables.
 
-Projections run through ops.linear: decode-shaped batches (M<=256) hit the
-hand-written weight-streaming gfx950 GEMM (ops/csrc/gemm_skinny.hip),
-prefill batches the TunableOp-tuned hipBLASLt/rocBLAS library GEMMs; the
-fused hot ops (rmsnorm+residual, rope, swiglu, attention, sampling) are the
-hand-written CDNA4 kernels behind llmapigateway_amd.ops.
+Projections run through ops.linear: decode-shaped batches (8 < M <= 256)
+hit the macro-tile LDS-staged gfx950 GEMM (ops/csrc/gemm_m256.hip) for the
+shapes its measured dispatch table wins (o/down; gate_up with the swiglu
+fused into the epilogue), the streaming skinny kernel
+(ops/csrc/gemm_skinny.hip) serves the M <= 16 latency regime without a
+fragment twin, and prefill batches, qkv and lm_head use the TunableOp-tuned
+hipBLASLt/rocBLAS library GEMMs. The o- and down-projections also produce
+the following RMSNorm (ops.linear_rmsnorm_residual): on the split-K decode
+path the slab reduction, residual add and norm are one kernel. The other hot
+ops (rope, attention, sampling) are the hand-written CDNA4 kernels behind
+llmapigateway_amd.ops.
 
 Tensor parallelism: construct with ``tp_group`` + a config pre-sharded via
 ModelConfig.scaled_for_tp; qkv/gate_up are column-sharded, o/down
@@ -225,6 +231,18 @@ class LlamaModel:
         h2.wait()
         return torch.cat([y1, y2], dim=0)
 
+    def _row_parallel_norm(self, x, w, w_swz, residual, norm_w):
+        """Row-parallel linear followed by the residual-add RMSNorm ->
+        (normed, residual). Without TP the two go through one op so the
+        decode path can fuse the norm into the split-K reduction; under TP
+        the all-reduce sits between GEMM and norm, so they stay separate."""
+        eps = self.config.rms_eps
+        if self.tp_group is None:
+            return ops.linear_rmsnorm_residual(x, w, w_swz, residual, norm_w, eps)
+        return ops.rmsnorm_residual(
+            self._row_parallel(x, w, w_swz), residual, norm_w, eps
+        )
+
     @torch.inference_mode()
     def forward(
         self,
@@ -240,14 +258,13 @@ class LlamaModel:
         ksc = k_scales if k_scales is not None else [None] * len(self.layers)
         vsc = v_scales if v_scales is not None else [None] * len(self.layers)
         h = F.embedding(batch.token_ids, self.embed)
-        residual = h  # placeholder; layer 0 sets the real residual stream
         T = h.shape[0]
+        # layer 0 norms the embeddings directly; every later input_norm (and
+        # the final norm) comes out of the previous layer's down-projection
+        x, residual = ops.rmsnorm(h, self.layers[0]["input_norm"], c.rms_eps), h
+        n_layers = len(self.layers)
 
         for i, layer in enumerate(self.layers):
-            if i == 0:
-                x, residual = ops.rmsnorm(h, layer["input_norm"], c.rms_eps), h
-            else:
-                x, residual = ops.rmsnorm_residual(h, residual, layer["input_norm"], c.rms_eps)
 
             qkv = ops.linear(x, layer["qkv"], layer.get("qkv_swz"))
             q, k, v = qkv.split([c.q_size, c.kv_size, c.kv_size], dim=-1)
@@ -296,20 +313,23 @@ class LlamaModel:
                     k_scale=ksc[i], v_scale=vsc[i],
                 )
 
-            h = self._row_parallel(
-                attn.reshape(T, c.q_size), layer["o"], layer.get("o_swz")
+            x, residual = self._row_parallel_norm(
+                attn.reshape(T, c.q_size), layer["o"], layer.get("o_swz"),
+                residual, layer["post_norm"],
             )
-
-            x, residual = ops.rmsnorm_residual(h, residual, layer["post_norm"], c.rms_eps)
-            h = self._row_parallel(
+            next_norm = (
+                self.layers[i + 1]["input_norm"] if i + 1 < n_layers
+                else self.final_norm
+            )
+            x, residual = self._row_parallel_norm(
                 ops.swiglu_linear(
                     x, layer["gate_up"], layer.get("gate_up_swz"),
                     layer.get("gate_up_int"),
                 ),
                 layer["down"], layer.get("down_swz"),
+                residual, next_norm,
             )
 
-        x, _ = ops.rmsnorm_residual(h, residual, self.final_norm, c.rms_eps)
         if batch.logits_indices is not None:
             x = x[batch.logits_indices]
         return ops.linear(x, self.lm_head).float()

@@ -432,6 +432,84 @@ def gemm_m256(
     return y
 
 
+def _reduce_norm_covers(N: int) -> bool:
+    """Row widths the fused split-K reduce + RMSNorm kernel covers (keep in
+    sync with gemm_reduce_rmsnorm_covers in csrc/gemm_skinny.hip)."""
+    return N % 512 == 0 and 0 < N <= 8192
+
+
+def gemm_m256_rmsnorm_residual(
+    x: torch.Tensor, w_frag: torch.Tensor, residual: torch.Tensor,
+    norm_w: torch.Tensor, eps: float, nf: int, nsk: int, variant: int = 0,
+    pipe: int = 0,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """rmsnorm_residual(x @ w.T, residual, norm_w) with the residual add and
+    the norm fused into the split-K slab reduction of gemm_m256 (one kernel
+    instead of reduce + norm; the bf16 y never touches HBM). residual is
+    updated in place, bit-identical to the unfused pair. Needs nsk > 1."""
+    M, K = x.shape
+    N = w_frag.shape[1] * 16
+    if nsk < 2:
+        raise ValueError("fused reduce+norm needs split-K slabs (nsk > 1)")
+    out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    ws = _skinny_scratch(x.device, nsk * M * N)
+    # y is not written on the fused path; `out` stands in for its shape check
+    _native().gemm_m256(
+        out, x, w_frag, ws, nsk, nf, variant, pipe, 0,
+        residual, norm_w, float(eps), out,
+    )
+    return out, residual
+
+
+def _m256_route(
+    x: torch.Tensor, w: torch.Tensor, w_swz: Optional[torch.Tensor]
+) -> Optional[dict]:
+    """gemm_m256 kwargs when linear() sends this call to the macro-tile
+    kernel, else None (library, skinny kernel or CPU)."""
+    M = x.shape[0]
+    if not (
+        x.is_cuda
+        and x.dim() == 2
+        and x.dtype == torch.bfloat16
+        and w.dtype == torch.bfloat16
+        and w.shape[0] % 64 == 0
+        and w.shape[0] <= _SKINNY_MAX_N
+        and w.shape[1] % 64 == 0
+        and x.is_contiguous()
+        and w.is_contiguous()
+        and w_swz is not None
+        and w_swz.dim() == 4
+        and 8 < M <= 256
+    ):
+        return None
+    return _m256_config(M, w.shape[0], w.shape[1])
+
+
+def linear_rmsnorm_residual(
+    x: torch.Tensor, w: torch.Tensor, w_swz: Optional[torch.Tensor],
+    residual: torch.Tensor, norm_w: torch.Tensor, eps: float = 1e-5,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(normed, residual) = rmsnorm_residual(linear(x, w, w_swz), residual,
+    norm_w, eps). Fused into the split-K reduction exactly when linear()
+    would pick gemm_m256 with nsk > 1 and the row width is covered; every
+    other case (CPU, library shapes, M <= 8, M > 256, the legacy k-major
+    twin, LLMAPI_NO_DECODE_FUSION=1) runs the two ops as before."""
+    if not x.is_cuda:
+        return reference.linear_rmsnorm_residual(x, w, residual, norm_w, eps)
+    if not os.environ.get("LLMAPI_NO_DECODE_FUSION"):
+        cfg = _m256_route(x, w, w_swz)
+        if (
+            cfg is not None
+            and cfg["nsk"] > 1
+            and _reduce_norm_covers(w.shape[0])
+            and residual.is_contiguous()
+        ):
+            return gemm_m256_rmsnorm_residual(
+                x, w_swz, residual, norm_w, eps, **cfg
+            )
+    return rmsnorm_residual(linear(x, w, w_swz), residual, norm_w, eps)
+
+
 def interleave_gate_up(w: torch.Tensor) -> torch.Tensor:
     """Row-permute a [gate; up] stacked weight [2I, K] into block-16
     interleaved order [g0..15, u0..15, g16..31, ...]: after
@@ -576,6 +654,8 @@ __all__ = [
     "kv_cache_write",
     "linear",
     "gemm_m256",
+    "gemm_m256_rmsnorm_residual",
+    "linear_rmsnorm_residual",
     "swizzle_weight",
     "swizzle_weight_frag",
     "attention_prefill",

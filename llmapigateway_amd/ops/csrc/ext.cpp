@@ -23,7 +23,7 @@ hipError_t launch_attention_prefill(void*, const void*, const void*, const void*
 hipError_t launch_sample(int64_t*, const float*, const float*, const float*, float*, int*, int, int, hipStream_t);
 hipError_t launch_topk_topp_filter(float*, const float*, const int*, int, int, hipStream_t);
 hipError_t launch_gemm_skinny(void*, float*, const void*, const void*, int, int, int, int, int, hipStream_t);
-hipError_t launch_gemm_m256(void*, float*, const void*, const void*, int, int, int, int, int, int, int, int, hipStream_t);
+hipError_t launch_gemm_m256(void*, float*, const void*, const void*, int, int, int, int, int, int, int, int, void*, const void*, float, void*, hipStream_t);
 }
 
 namespace {
@@ -313,7 +313,10 @@ void gemm_skinny(torch::Tensor y, torch::Tensor x, torch::Tensor w,
 
 void gemm_m256(torch::Tensor y, torch::Tensor x, torch::Tensor w_frag,
                c10::optional<torch::Tensor> workspace, int64_t nsk,
-               int64_t nf, int64_t variant, int64_t pipe, int64_t swiglu) {
+               int64_t nf, int64_t variant, int64_t pipe, int64_t swiglu,
+               c10::optional<torch::Tensor> residual,
+               c10::optional<torch::Tensor> norm_weight, double eps,
+               c10::optional<torch::Tensor> out) {
     check_bf16(x, "x");
     check_bf16(w_frag, "w_frag");
     check_bf16(y, "y");
@@ -335,10 +338,35 @@ void gemm_m256(torch::Tensor y, torch::Tensor x, torch::Tensor w_frag,
                     "workspace must be fp32 with >= nsk*M*N elements");
         ws = workspace->data_ptr<float>();
     }
+    // fused split-K reduce + residual add + RMSNorm: residual is updated
+    // in place, out receives the normed rows, y is not written
+    void *res_p = nullptr, *nw_p = nullptr, *out_p = nullptr;
+    if (residual.has_value() || norm_weight.has_value() || out.has_value()) {
+        TORCH_CHECK(residual.has_value() && norm_weight.has_value() &&
+                    out.has_value(),
+                    "residual, norm_weight and out go together");
+        TORCH_CHECK(nsk > 1 && !swiglu && ws != nullptr,
+                    "fused reduce+norm needs split-K (nsk > 1) slabs");
+        check_bf16(*residual, "residual");
+        check_bf16(*norm_weight, "norm_weight");
+        check_bf16(*out, "out");
+        TORCH_CHECK(residual->is_contiguous() && out->is_contiguous() &&
+                    norm_weight->is_contiguous());
+        TORCH_CHECK(residual->dim() == 2 && residual->size(0) == M &&
+                    residual->size(1) == N && out->dim() == 2 &&
+                    out->size(0) == M && out->size(1) == N &&
+                    norm_weight->numel() == N,
+                    "residual/out must be [M, N], norm_weight [N]");
+        TORCH_CHECK(N % 512 == 0 && N <= 8192,
+                    "fused reduce+norm covers N % 512 == 0, N <= 8192");
+        res_p = residual->data_ptr();
+        nw_p = norm_weight->data_ptr();
+        out_p = out->data_ptr();
+    }
     CHECK_HIP(launch_gemm_m256(y.data_ptr(), ws, x.data_ptr(),
                                w_frag.data_ptr(), M, N, K, (int)nsk, (int)nf,
-                               (int)variant, (int)pipe, (int)swiglu,
-                               current_stream()));
+                               (int)variant, (int)pipe, (int)swiglu, res_p,
+                               nw_p, (float)eps, out_p, current_stream()));
 }
 
 }  // namespace
@@ -358,7 +386,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gemm_skinny", &gemm_skinny,
           "skinny-M weight-streaming GEMM y = x @ w.T (decode projections)");
     m.def("gemm_m256", &gemm_m256,
-          "macro-tile LDS-staged decode GEMM y = x @ w.T (M <= 256)");
+          "macro-tile LDS-staged decode GEMM y = x @ w.T (M <= 256); with "
+          "residual/norm_weight/out the split-K reduce also adds the "
+          "residual and RMS-normalizes",
+          pybind11::arg("y"), pybind11::arg("x"), pybind11::arg("w_frag"),
+          pybind11::arg("workspace"), pybind11::arg("nsk"),
+          pybind11::arg("nf"), pybind11::arg("variant"),
+          pybind11::arg("pipe"), pybind11::arg("swiglu"),
+          pybind11::arg("residual") = pybind11::none(),
+          pybind11::arg("norm_weight") = pybind11::none(),
+          pybind11::arg("eps") = 1e-5,
+          pybind11::arg("out") = pybind11::none());
 
     pybind11::class_<BlockAllocator>(m, "BlockAllocator")
         .def(pybind11::init<int64_t>())

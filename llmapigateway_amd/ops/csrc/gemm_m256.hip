@@ -684,6 +684,10 @@ __global__ void gemm_m256pc_kernel(
 
 extern "C" hipError_t launch_gemm_reduce(void*, const float*, int64_t, int,
                                          hipStream_t);  // gemm_skinny.hip
+extern "C" int gemm_reduce_rmsnorm_covers(int N);       // gemm_skinny.hip
+extern "C" hipError_t launch_gemm_reduce_rmsnorm(void*, void*, const float*,
+                                                 const void*, float, int, int,
+                                                 int, hipStream_t);
 
 // nf: 4 (BN=64) or 8 (BN=128). M <= 256; N % (16*nf) == 0; K % 64 == 0.
 // variant: 0 = glds-staged (DMA pipeline, depth per `pipe`),
@@ -694,11 +698,20 @@ extern "C" hipError_t launch_gemm_reduce(void*, const float*, int64_t, int,
 //          HBM latency covered on the W stream; 4=(BK64,NBUF2,nf4) and
 //          5=(BK32,NBUF3,nf4) fit 2 blocks/CU so a second block fills the
 //          barrier-lockstep wait gaps.
+// residual/norm_weight/norm_out (all or none): the split-K reduce becomes
+// the fused reduce + residual-add + RMSNorm (gemm_skinny.hip) — residual
+// is updated in place, norm_out receives the normed row and y is not
+// written. Needs nsk > 1 (the slabs are the fusion point) and a covered N.
 extern "C" hipError_t launch_gemm_m256(
     void* y, float* workspace, const void* x, const void* w, int M, int N,
     int K, int nsk, int nf, int variant, int pipe, int swiglu,
+    void* residual, const void* norm_weight, float eps, void* norm_out,
     hipStream_t stream) {
     if (M <= 0 || M > 256) return hipErrorInvalidValue;
+    const bool fuse_norm = residual != nullptr;
+    if (fuse_norm && (norm_weight == nullptr || norm_out == nullptr ||
+                      nsk < 2 || swiglu || !gemm_reduce_rmsnorm_covers(N)))
+        return hipErrorInvalidValue;
     if (nsk < 1 || (nsk > 1 && workspace == nullptr)) return hipErrorInvalidValue;
     if ((K % GM_BK) != 0) return hipErrorInvalidValue;
     // fused swiglu epilogue: y is [M, N/2], single-pass only (the fp32
@@ -713,6 +726,10 @@ extern "C" hipError_t launch_gemm_m256(
         else PC_L(false);
 #undef PC_L
         HIP_CHECK_LAST();
+        if (fuse_norm)
+            return launch_gemm_reduce_rmsnorm(norm_out, residual, workspace,
+                                              norm_weight, eps, M, N, nsk,
+                                              stream);
         if (nsk > 1)
             return launch_gemm_reduce(y, workspace, (int64_t)M * N, nsk, stream);
         return hipSuccess;
@@ -793,6 +810,9 @@ extern "C" hipError_t launch_gemm_m256(
 #undef GM_L1
 #undef GM_L2
     HIP_CHECK_LAST();
+    if (fuse_norm)
+        return launch_gemm_reduce_rmsnorm(norm_out, residual, workspace,
+                                          norm_weight, eps, M, N, nsk, stream);
     if (nsk > 1) {
         const int64_t mn = (int64_t)M * N;  // N % 64 == 0 -> mn % 4 == 0
         return launch_gemm_reduce(y, workspace, mn, nsk, stream);

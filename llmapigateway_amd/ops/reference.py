@@ -39,6 +39,17 @@ def rmsnorm_residual(
     return rmsnorm(r, weight, eps), r
 
 
+def linear_rmsnorm_residual(
+    x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor,
+    norm_w: torch.Tensor, eps: float = 1e-5,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Projection followed by the residual-add norm (what the GPU path
+    fuses into the split-K reduction): y = x @ w.T rounded to the input
+    dtype, then rmsnorm_residual(y, residual)."""
+    y = torch.nn.functional.linear(x, w)
+    return rmsnorm_residual(y, residual, norm_w, eps)
+
+
 def build_rope_cache(
     max_positions: int, head_dim: int, theta: float = 500000.0, device="cpu"
 ) -> torch.Tensor:
