@@ -49,6 +49,7 @@ class EngineSpec(BaseModel):
     max_batch_size: Optional[int] = None
     kv_block_size: Optional[int] = None
     kv_dtype: str = "auto"               # "auto" (= compute dtype) | "fp8"
+    weight_dtype: str = "auto"           # "auto" (= compute dtype) | "fp8" (e4m3 projections)
     fail_rate: float = 0.0               # failure injection: P(request fails)
     fail_requests: Optional[int] = None  # failure injection: fail first N requests
 
@@ -80,6 +81,8 @@ class ProviderDetails(BaseModel):
                 updates["dtype"] = q["dtype"][0]
             if "kv_dtype" in q:
                 updates["kv_dtype"] = q["kv_dtype"][0]
+            if "weight_dtype" in q:
+                updates["weight_dtype"] = q["weight_dtype"][0]
             if "fail_rate" in q:
                 updates["fail_rate"] = float(q["fail_rate"][0])
             if updates:

@@ -167,6 +167,7 @@ class LLMEngine:
         prefix_caching: bool = False,
         prefill_budget: int = 4096,
         kv_dtype: str = "auto",
+        weight_dtype: str = "auto",
         tokenizer: Optional[object] = None,
         admit_min_batch: Optional[int] = None,
         admit_max_wait: Optional[float] = None,
@@ -191,10 +192,13 @@ class LLMEngine:
 
         if self.device.type == "cuda":
             torch.cuda.set_device(self.device)
+        if weight_dtype == "auto":
+            weight_dtype = os.environ.get("LLMAPI_WEIGHT_DTYPE", "auto")
+        self.weight_dtype = weight_dtype  # "auto" (= compute dtype) | "fp8"
         self.model = LlamaModel(
             config, device=self.device, dtype=dtype, seed=seed,
             tp_group=tp_group, tp_rank=tp_rank, tp_size=tp_size,
-            full_config=full_config,
+            full_config=full_config, weight_dtype=weight_dtype,
         )
         if kv_dtype == "auto":
             kv_dtype = os.environ.get("LLMAPI_KV_DTYPE", "auto")

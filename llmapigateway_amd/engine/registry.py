@@ -131,6 +131,8 @@ class EngineRegistry:
             key += f"/k{spec.kv_block_size}"
         if spec.kv_dtype not in ("auto", None):
             key += f"/kv{spec.kv_dtype}"
+        if spec.weight_dtype not in ("auto", None):
+            key += f"/w{spec.weight_dtype}"
         if spec.dtype not in ("bfloat16", None):
             key += f"/{spec.dtype}"
         return key
@@ -168,6 +170,7 @@ class EngineRegistry:
                     dtype="float16" if spec.dtype in ("float16", "fp16") else "bfloat16",
                     max_batch_size=spec.max_batch_size or self.settings.engine_max_batch_size,
                     kv_block_size=spec.kv_block_size or self.settings.engine_kv_block_size,
+                    weight_dtype=spec.weight_dtype,
                 )
                 handle = _TPGroupHandle(client, key)
                 self._engines[key] = handle
@@ -188,6 +191,7 @@ class EngineRegistry:
                 prefix_caching=self.settings.engine_prefix_caching,
                 use_hipgraph=None if self.settings.engine_use_hipgraph else False,
                 kv_dtype=spec.kv_dtype,
+                weight_dtype=spec.weight_dtype,
             )
             if engine.graph_runner is not None:
                 logger.info("pre-capturing decode hipGraphs for %s", key)
@@ -708,6 +712,7 @@ class EngineRegistry:
             row = {
                 "engine": key,
                 "model": eng.full_config.name,
+                "weight_dtype": getattr(eng, "weight_dtype", "auto"),
                 **{k: int(v) for k, v in eng.stats.items()},
             }
             if hasattr(eng, "kv"):  # single-process engine

@@ -59,6 +59,7 @@ def _worker_main(
     seed: int,
     inbox,
     outbox,
+    weight_dtype: str = "auto",
 ) -> None:
     # fresh interpreter (spawn): do the heavy imports here
     import torch
@@ -92,6 +93,7 @@ def _worker_main(
             None if have_cuda and not os.environ.get("LLMAPI_NO_TP_HIPGRAPH")
             else False
         ),
+        weight_dtype=weight_dtype,
         tp_group=dist.group.WORLD,
         tp_rank=rank,
         tp_size=world,
@@ -243,6 +245,7 @@ class TPEngineClient:
         max_model_len: Optional[int] = None,
         seed: int = 0,
         start_timeout: float = 600.0,
+        weight_dtype: str = "auto",
     ):
         from ..models.configs import get_model_config
         from .tokenizer import get_tokenizer
@@ -251,6 +254,7 @@ class TPEngineClient:
         self.tokenizer = get_tokenizer("auto", self.full_config.vocab_size)
         self.max_model_len = max_model_len or self.full_config.max_positions
         self.tp = tp
+        self.weight_dtype = weight_dtype
         ctx = mp.get_context("spawn")
         self.inbox = ctx.Queue()
         self.outbox = ctx.Queue()
@@ -261,6 +265,7 @@ class TPEngineClient:
                 args=(
                     r, tp, port, model, dtype, max_batch_size, kv_block_size,
                     num_blocks, self.max_model_len, seed, self.inbox, self.outbox,
+                    weight_dtype,
                 ),
                 daemon=True,
                 name=f"tp-worker-{r}",

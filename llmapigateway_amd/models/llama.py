@@ -79,7 +79,15 @@ class LlamaModel:
         tp_rank: int = 0,
         tp_size: int = 1,
         full_config: Optional[ModelConfig] = None,
+        weight_dtype: str = "auto",
     ):
+        if weight_dtype not in ("auto", "fp8"):
+            raise ValueError(f"weight_dtype must be 'auto' or 'fp8', got {weight_dtype!r}")
+        # "fp8": the four projections of every layer are held as e4m3 bits
+        # (fragment-major, ops.swizzle_weight_frag_fp8) plus one fp32 scale
+        # per output channel, and run through ops.linear_w8; embeddings,
+        # lm_head and norms stay in `dtype`
+        self.weight_dtype = weight_dtype
         self.config = config
         self.full_config = full_config or config
         self.device = torch.device(device)
@@ -123,11 +131,21 @@ class LlamaModel:
         std = 0.02
         out_std = 0.02 / math.sqrt(2 * c.num_layers)
         self.embed = mk(fc.vocab_size, hidden, std)
+        fp8 = self.weight_dtype == "fp8"
         for _ in range(c.num_layers):
             qkv_full = mk(fc.q_size + 2 * fc.kv_size, hidden, std)
             o_full = mk(hidden, fc.q_size, out_std)
             gu_full = mk(2 * fc.intermediate_size, hidden, std)
             down_full = mk(hidden, fc.intermediate_size, out_std)
+            if fp8:
+                # quantise the FULL matrices layer by layer (peak memory
+                # stays near the fp8 size), then shard bits and scales: TP=N
+                # stays a pure sharding of the TP=1 quantised model
+                self.layers.append(
+                    self._fp8_layer(qkv_full, o_full, gu_full, down_full)
+                )
+                del qkv_full, o_full, gu_full, down_full
+                continue
             self.layers.append(
                 {
                     "input_norm": torch.ones(hidden, dtype=self.dtype, device=self.device),
@@ -145,6 +163,104 @@ class LlamaModel:
         self.final_norm = torch.ones(hidden, dtype=self.dtype, device=self.device)
         self.lm_head = self.embed if c.tie_embeddings else mk(self.full_config.vocab_size, hidden, std)
 
+        if fp8:
+            self._reserve_w8_buffer()
+            return  # no bf16 matrices, so no bf16 twins
+        self._build_twins()
+
+    def _fp8_layer(self, qkv_full, o_full, gu_full, down_full) -> Dict[str, torch.Tensor]:
+        """One layer's dict in fp8 mode: `<name>_q8` (fragment-major e4m3
+        bits) and `<name>_s8` (fp32 scale per output channel) for the four
+        projections, from the full (unsharded) matrices."""
+        from ..parallel.tp import shard_gate_up, shard_qkv, shard_row
+
+        fc, tpr, tps = self.full_config, self.tp_rank, self.tp_size
+        hidden = self.config.hidden_size
+        layer: Dict[str, torch.Tensor] = {
+            "input_norm": torch.ones(hidden, dtype=self.dtype, device=self.device),
+            "post_norm": torch.ones(hidden, dtype=self.dtype, device=self.device),
+        }
+        for name, full in (
+            ("qkv", qkv_full), ("o", o_full), ("gate_up", gu_full), ("down", down_full)
+        ):
+            q, s = ops.fp8_quantize_weight(full)
+            if tps > 1:
+                if name == "qkv":
+                    q = shard_qkv(q, tpr, tps, fc.q_size, fc.kv_size)
+                    s = shard_qkv(s, tpr, tps, fc.q_size, fc.kv_size)
+                elif name == "gate_up":
+                    q = shard_gate_up(q, tpr, tps, fc.intermediate_size)
+                    s = shard_gate_up(s, tpr, tps, fc.intermediate_size)
+                else:  # row-parallel: every rank keeps all output channels
+                    q = shard_row(q, tpr, tps)
+            self._store_w8(layer, name, q, s)
+        return layer
+
+    @staticmethod
+    def _store_w8(layer, name: str, q: torch.Tensor, s: torch.Tensor) -> None:
+        if q.shape[0] % 64 or q.shape[1] % 64:
+            raise ValueError(
+                f"fp8 weights need projection shapes in multiples of 64; "
+                f"{name} is {tuple(q.shape)}"
+            )
+        layer[name + "_q8"] = ops.swizzle_weight_frag_fp8(q)
+        layer[name + "_s8"] = s.contiguous()
+
+    def _reserve_w8_buffer(self) -> None:
+        """The M > 256 route dequantises into one per-device bf16 buffer:
+        size it for the largest projection now, so captured graphs never
+        see it move."""
+        if self.device.type != "cuda":
+            return
+        # hand the quantiser's temporaries (full bf16 matrices, fp32 copies)
+        # back to the device first: the KV pool is sized from free memory
+        torch.cuda.empty_cache()
+        ops.w8_reserve_dequant(
+            self.device,
+            max(
+                layer[name + "_q8"].numel()
+                for layer in self.layers
+                for name in ("qkv", "o", "gate_up", "down")
+            ),
+        )
+
+    @torch.inference_mode()
+    def quantize_weights_(self, mode: str = "fp8", simulate: bool = False) -> "LlamaModel":
+        """Quantise the qkv/o/gate_up/down projections of a bf16 model in
+        place. simulate=False leaves the model as weight_dtype="fp8" builds
+        it (fp8 twin + scale only). simulate=True is fake-quant: every
+        projection becomes its dequantised value in the model dtype and the
+        bf16 twins are rebuilt — the same maths on the existing kernels, as
+        an oracle and an accuracy A/B."""
+        if mode != "fp8":
+            raise ValueError(f"unknown quantisation mode {mode!r}")
+        if self.weight_dtype == "fp8":
+            raise RuntimeError("weights are already fp8")
+        if self.tp_size > 1:
+            # row shards would get per-shard scales: not the TP=1 model
+            raise RuntimeError(
+                "quantize_weights_ works on an unsharded model; under tensor "
+                "parallelism construct with weight_dtype='fp8'"
+            )
+        names = ("qkv", "o", "gate_up", "down")
+        for layer in self.layers:
+            for key in [k for k in layer if k.endswith(("_swz", "_int"))]:
+                del layer[key]
+            for name in names:
+                q, s = ops.fp8_quantize_weight(layer[name])
+                if simulate:
+                    layer[name] = ops.fp8_dequantize_weight(q, s, self.dtype)
+                else:
+                    del layer[name]
+                    self._store_w8(layer, name, q, s)
+        if simulate:
+            self._build_twins()
+        else:
+            self.weight_dtype = "fp8"
+            self._reserve_w8_buffer()
+        return self
+
+    def _build_twins(self) -> None:
         # Fragment-major twins of the decode projections for the
         # macro-tile LDS-staged GEMM (ops/csrc/gemm_m256.hip) — ON by
         # default: the twin copy costs ~weights-again for the projections
@@ -195,12 +311,12 @@ class LlamaModel:
                     )
 
     def param_bytes(self) -> int:
-        total = self.embed.numel() + self.final_norm.numel()
+        tensors = [self.embed, self.final_norm]
         if self.lm_head is not self.embed:
-            total += self.lm_head.numel()
+            tensors.append(self.lm_head)
         for layer in self.layers:
-            total += sum(t.numel() for t in layer.values())
-        return total * self.embed.element_size()
+            tensors.extend(layer.values())
+        return sum(t.numel() * t.element_size() for t in tensors)
 
     # ---- forward ----
     def _maybe_all_reduce(self, x: torch.Tensor) -> torch.Tensor:
@@ -208,39 +324,50 @@ class LlamaModel:
             dist.all_reduce(x, group=self.tp_group)
         return x
 
-    def _row_parallel(self, x: torch.Tensor, w: torch.Tensor,
-                      w_swz=None) -> torch.Tensor:
+    def _linear(self, x: torch.Tensor, layer, name: str) -> torch.Tensor:
+        if self.weight_dtype == "fp8":
+            return ops.linear_w8(x, layer[name + "_q8"], layer[name + "_s8"])
+        return ops.linear(x, layer[name], layer.get(name + "_swz"))
+
+    def _row_parallel(self, x: torch.Tensor, layer, name: str) -> torch.Tensor:
         """Row-parallel linear with comm/compute overlap: split the token
         batch in two, launch the first half's all-reduce asynchronously
         while the second half's GEMM runs (overlap the 2
         all-reduces/layer with compute). Falls back to the plain form for
         tiny batches or TP=1."""
         if self.tp_group is None:
-            return ops.linear(x, w, w_swz)
+            return self._linear(x, layer, name)
         T = x.shape[0]
         if T < 32:  # split overhead exceeds the overlap win
-            y = ops.linear(x, w, w_swz)
+            y = self._linear(x, layer, name)
             dist.all_reduce(y, group=self.tp_group)
             return y
         half = T // 2
-        y1 = ops.linear(x[:half], w, w_swz)
+        y1 = self._linear(x[:half], layer, name)
         h1 = dist.all_reduce(y1, group=self.tp_group, async_op=True)
-        y2 = ops.linear(x[half:], w, w_swz)
+        y2 = self._linear(x[half:], layer, name)
         h2 = dist.all_reduce(y2, group=self.tp_group, async_op=True)
         h1.wait()
         h2.wait()
         return torch.cat([y1, y2], dim=0)
 
-    def _row_parallel_norm(self, x, w, w_swz, residual, norm_w):
+    def _row_parallel_norm(self, x, layer, name, residual, norm_w):
         """Row-parallel linear followed by the residual-add RMSNorm ->
         (normed, residual). Without TP the two go through one op so the
         decode path can fuse the norm into the split-K reduction; under TP
         the all-reduce sits between GEMM and norm, so they stay separate."""
         eps = self.config.rms_eps
         if self.tp_group is None:
-            return ops.linear_rmsnorm_residual(x, w, w_swz, residual, norm_w, eps)
+            if self.weight_dtype == "fp8":
+                return ops.linear_w8_rmsnorm_residual(
+                    x, layer[name + "_q8"], layer[name + "_s8"], residual,
+                    norm_w, eps,
+                )
+            return ops.linear_rmsnorm_residual(
+                x, layer[name], layer.get(name + "_swz"), residual, norm_w, eps
+            )
         return ops.rmsnorm_residual(
-            self._row_parallel(x, w, w_swz), residual, norm_w, eps
+            self._row_parallel(x, layer, name), residual, norm_w, eps
         )
 
     @torch.inference_mode()
@@ -266,7 +393,7 @@ class LlamaModel:
 
         for i, layer in enumerate(self.layers):
 
-            qkv = ops.linear(x, layer["qkv"], layer.get("qkv_swz"))
+            qkv = self._linear(x, layer, "qkv")
             q, k, v = qkv.split([c.q_size, c.kv_size, c.kv_size], dim=-1)
             q = q.view(T, c.num_heads, c.head_dim)
             k = k.view(T, c.num_kv_heads, c.head_dim)
@@ -314,20 +441,22 @@ class LlamaModel:
                 )
 
             x, residual = self._row_parallel_norm(
-                attn.reshape(T, c.q_size), layer["o"], layer.get("o_swz"),
+                attn.reshape(T, c.q_size), layer, "o",
                 residual, layer["post_norm"],
             )
             next_norm = (
                 self.layers[i + 1]["input_norm"] if i + 1 < n_layers
                 else self.final_norm
             )
-            x, residual = self._row_parallel_norm(
-                ops.swiglu_linear(
+            if self.weight_dtype == "fp8":
+                act = ops.swiglu(self._linear(x, layer, "gate_up"))
+            else:
+                act = ops.swiglu_linear(
                     x, layer["gate_up"], layer.get("gate_up_swz"),
                     layer.get("gate_up_int"),
-                ),
-                layer["down"], layer.get("down_swz"),
-                residual, next_norm,
+                )
+            x, residual = self._row_parallel_norm(
+                act, layer, "down", residual, next_norm,
             )
 
         if batch.logits_indices is not None:

@@ -42,6 +42,12 @@ if torch.version.hip and os.path.exists(_TUNE_BASE.replace(".csv", "0.csv")):
 
 from . import reference
 from .reference import build_rope_cache  # re-export (host-side table builder)
+from .reference import (  # re-export (fp8 weight quantisation scheme)
+    fp8_dequantize_weight,
+    fp8_quantize_weight,
+    swizzle_weight_frag_fp8,
+    unswizzle_weight_frag_fp8,
+)
 
 _C = None
 _C_ERR: Optional[str] = None
@@ -618,6 +624,118 @@ def linear(
     return torch.nn.functional.linear(x, w)
 
 
+# ---- fp8 (e4m3) weights: W8A16 decode GEMM (csrc/gemm_w8.hip) ----
+_W8_MAX_M = 256  # keep in sync with W8_MAX_M in gemm_w8.hip
+# per-device bf16 buffer the M > 256 route dequantises into; reserved once
+# at model init (w8_reserve_dequant) so captured graphs never see it move
+_w8_dq: dict = {}
+_w8_dq_retired: list = []
+
+
+def _w8_nsk(N: int, K: int) -> int:
+    """The _skinny_nsk rule at the kernel's k64 step granularity."""
+    tiles = N // 64
+    nsk = max(1, -(-256 // tiles))
+    return min(nsk, max(1, (K // 64) // 8), 8)
+
+
+def w8_reserve_dequant(device, numel: int) -> torch.Tensor:
+    """Make the per-device dequantisation buffer hold at least numel bf16."""
+    device = torch.device(device)
+    buf = _w8_dq.get(device.index)
+    if buf is None or buf.numel() < numel:
+        if buf is not None:
+            _w8_dq_retired.append(buf)  # a hipGraph may still replay into it
+        buf = torch.empty(numel, dtype=torch.bfloat16, device=device)
+        _w8_dq[device.index] = buf
+    return buf
+
+
+def dequant_w8(
+    q_frag: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor] = None
+) -> torch.Tensor:
+    """Fragment-major fp8 twin + scale -> row-major bf16 [N, K]; into `out`
+    when given, else into the per-device buffer (valid until the next call)."""
+    K, N = q_frag.shape[0] * 64, q_frag.shape[1] * 16
+    if not q_frag.is_cuda:
+        w = reference.fp8_dequantize_weight(
+            reference.unswizzle_weight_frag_fp8(q_frag), scale, torch.bfloat16
+        )
+        if out is not None:
+            out.copy_(w)
+            return out
+        return w
+    if out is None:
+        out = w8_reserve_dequant(q_frag.device, N * K)[: N * K].view(N, K)
+    _native().dequant_w8(out, q_frag, scale)
+    return out
+
+
+def _w8_gpu_check(x: torch.Tensor) -> None:
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or not x.is_contiguous():
+        raise RuntimeError(
+            "linear_w8 on GPU needs a contiguous 2-D bf16 activation "
+            f"(got dim={x.dim()}, dtype={x.dtype}, contiguous={x.is_contiguous()})"
+        )
+
+
+def linear_w8(
+    x: torch.Tensor, q_frag: torch.Tensor, scale: torch.Tensor,
+    nsk: Optional[int] = None,
+) -> torch.Tensor:
+    """y = x @ (scale * q).T with q the fragment-major fp8 e4m3 twin
+    (swizzle_weight_frag_fp8) and scale one fp32 per output channel.
+    GPU: M <= 256 runs the W8A16 streaming kernel (csrc/gemm_w8.hip),
+    larger M dequantises into the per-device bf16 buffer and calls the
+    library GEMM. CPU: the reference."""
+    if not x.is_cuda:
+        return reference.linear_w8(
+            x, reference.unswizzle_weight_frag_fp8(q_frag), scale
+        )
+    _w8_gpu_check(x)
+    M, K = x.shape
+    N = q_frag.shape[1] * 16
+    if M > _W8_MAX_M:
+        return torch.nn.functional.linear(x, dequant_w8(q_frag, scale))
+    if nsk is None:
+        nsk = _w8_nsk(N, K)
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    ws = _skinny_scratch(x.device, nsk * M * N) if nsk > 1 else None
+    _native().gemm_w8(y, x, q_frag, scale, ws, nsk)
+    return y
+
+
+def linear_w8_rmsnorm_residual(
+    x: torch.Tensor, q_frag: torch.Tensor, scale: torch.Tensor,
+    residual: torch.Tensor, norm_w: torch.Tensor, eps: float = 1e-5,
+    nsk: Optional[int] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(normed, residual) = rmsnorm_residual(linear_w8(x, q_frag, scale),
+    residual, norm_w, eps). On the split-K kernel route (nsk > 1) with a
+    covered row width the residual add and the norm run inside the slab
+    reduction; bit-identical to the unfused pair, which every other case
+    runs (LLMAPI_NO_DECODE_FUSION=1 forces it)."""
+    if x.is_cuda and not os.environ.get("LLMAPI_NO_DECODE_FUSION"):
+        _w8_gpu_check(x)
+        M, K = x.shape
+        N = q_frag.shape[1] * 16
+        k = _w8_nsk(N, K) if nsk is None else nsk
+        if (
+            M <= _W8_MAX_M
+            and k > 1
+            and _reduce_norm_covers(N)
+            and residual.is_contiguous()
+        ):
+            out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+            ws = _skinny_scratch(x.device, k * M * N)
+            # y is not written on the fused path; `out` stands in for it
+            _native().gemm_w8(
+                out, x, q_frag, scale, ws, k, residual, norm_w, float(eps), out
+            )
+            return out, residual
+    return rmsnorm_residual(linear_w8(x, q_frag, scale, nsk), residual, norm_w, eps)
+
+
 def topk_topp_filter(
     logits: torch.Tensor, topp: torch.Tensor, topk: torch.Tensor
 ) -> torch.Tensor:
@@ -658,6 +776,14 @@ __all__ = [
     "linear_rmsnorm_residual",
     "swizzle_weight",
     "swizzle_weight_frag",
+    "fp8_quantize_weight",
+    "fp8_dequantize_weight",
+    "swizzle_weight_frag_fp8",
+    "unswizzle_weight_frag_fp8",
+    "linear_w8",
+    "linear_w8_rmsnorm_residual",
+    "dequant_w8",
+    "w8_reserve_dequant",
     "attention_prefill",
     "attention_decode",
     "sample",

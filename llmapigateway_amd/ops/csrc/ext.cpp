@@ -24,6 +24,8 @@ hipError_t launch_sample(int64_t*, const float*, const float*, const float*, flo
 hipError_t launch_topk_topp_filter(float*, const float*, const int*, int, int, hipStream_t);
 hipError_t launch_gemm_skinny(void*, float*, const void*, const void*, int, int, int, int, int, hipStream_t);
 hipError_t launch_gemm_m256(void*, float*, const void*, const void*, int, int, int, int, int, int, int, int, void*, const void*, float, void*, hipStream_t);
+hipError_t launch_gemm_w8(void*, float*, const void*, const void*, const float*, int, int, int, int, void*, const void*, float, void*, hipStream_t);
+hipError_t launch_dequant_w8(void*, const void*, const float*, int, int, hipStream_t);
 }
 
 namespace {
@@ -369,6 +371,87 @@ void gemm_m256(torch::Tensor y, torch::Tensor x, torch::Tensor w_frag,
                                nw_p, (float)eps, out_p, current_stream()));
 }
 
+// fragment-major fp8 weight twin [K/64, N/16, 64, 16] (uint8 e4m3 bits) and
+// its per-output-channel fp32 scale [N]; returns N
+int check_w8(const torch::Tensor& q_frag, const torch::Tensor& scale, int K) {
+    TORCH_CHECK(q_frag.is_cuda() && scale.is_cuda(), "q_frag/scale must be on GPU");
+    TORCH_CHECK(q_frag.scalar_type() == torch::kUInt8,
+                "q_frag must be uint8 (e4m3 bits)");
+    TORCH_CHECK(scale.scalar_type() == torch::kFloat32, "scale must be fp32");
+    TORCH_CHECK(q_frag.is_contiguous() && scale.is_contiguous());
+    TORCH_CHECK(K > 0 && K % 64 == 0, "K must be a positive multiple of 64");
+    TORCH_CHECK(q_frag.dim() == 4 && q_frag.size(0) == K / 64 &&
+                q_frag.size(2) == 64 && q_frag.size(3) == 16,
+                "q_frag must be the fragment-major [K/64, N/16, 64, 16] twin");
+    const int N = q_frag.size(1) * 16;
+    TORCH_CHECK(N > 0 && N % 64 == 0, "N must be a positive multiple of 64");
+    TORCH_CHECK(scale.dim() == 1 && scale.numel() == N,
+                "scale must hold one fp32 per output channel ([N])");
+    return N;
+}
+
+void gemm_w8(torch::Tensor y, torch::Tensor x, torch::Tensor q_frag,
+             torch::Tensor scale, c10::optional<torch::Tensor> workspace,
+             int64_t nsk, c10::optional<torch::Tensor> residual,
+             c10::optional<torch::Tensor> norm_weight, double eps,
+             c10::optional<torch::Tensor> out) {
+    check_bf16(x, "x");
+    check_bf16(y, "y");
+    TORCH_CHECK(x.is_contiguous() && y.is_contiguous());
+    TORCH_CHECK(x.dim() == 2 && y.dim() == 2);
+    const int M = x.size(0), K = x.size(1);
+    TORCH_CHECK(M >= 1 && M <= 256, "gemm_w8 covers 1 <= M <= 256");
+    const int N = check_w8(q_frag, scale, K);
+    TORCH_CHECK(y.size(0) == M && y.size(1) == N);
+    TORCH_CHECK(nsk >= 1 && nsk <= K / 64, "nsk must be in [1, K/64]");
+    float* ws = nullptr;
+    if (workspace.has_value() && workspace->defined()) {
+        TORCH_CHECK(workspace->is_cuda() &&
+                    workspace->scalar_type() == torch::kFloat32 &&
+                    workspace->is_contiguous() &&
+                    workspace->numel() >= nsk * (int64_t)M * N,
+                    "workspace must be fp32 with >= nsk*M*N elements");
+        ws = workspace->data_ptr<float>();
+    }
+    TORCH_CHECK(nsk == 1 || ws != nullptr, "split-K needs a workspace");
+    void *res_p = nullptr, *nw_p = nullptr, *out_p = nullptr;
+    if (residual.has_value() || norm_weight.has_value() || out.has_value()) {
+        TORCH_CHECK(residual.has_value() && norm_weight.has_value() &&
+                    out.has_value(),
+                    "residual, norm_weight and out go together");
+        TORCH_CHECK(nsk > 1, "fused reduce+norm needs split-K (nsk > 1) slabs");
+        check_bf16(*residual, "residual");
+        check_bf16(*norm_weight, "norm_weight");
+        check_bf16(*out, "out");
+        TORCH_CHECK(residual->is_contiguous() && out->is_contiguous() &&
+                    norm_weight->is_contiguous());
+        TORCH_CHECK(residual->dim() == 2 && residual->size(0) == M &&
+                    residual->size(1) == N && out->dim() == 2 &&
+                    out->size(0) == M && out->size(1) == N &&
+                    norm_weight->numel() == N,
+                    "residual/out must be [M, N], norm_weight [N]");
+        TORCH_CHECK(N % 512 == 0 && N <= 8192,
+                    "fused reduce+norm covers N % 512 == 0, N <= 8192");
+        res_p = residual->data_ptr();
+        nw_p = norm_weight->data_ptr();
+        out_p = out->data_ptr();
+    }
+    CHECK_HIP(launch_gemm_w8(y.data_ptr(), ws, x.data_ptr(), q_frag.data_ptr(),
+                             scale.data_ptr<float>(), M, N, K, (int)nsk, res_p,
+                             nw_p, (float)eps, out_p, current_stream()));
+}
+
+void dequant_w8(torch::Tensor out, torch::Tensor q_frag, torch::Tensor scale) {
+    check_bf16(out, "out");
+    TORCH_CHECK(out.is_contiguous() && out.dim() == 2);
+    const int K = out.size(1);
+    const int N = check_w8(q_frag, scale, K);
+    TORCH_CHECK(out.size(0) == N, "out must be [N, K]");
+    CHECK_HIP(launch_dequant_w8(out.data_ptr(), q_frag.data_ptr(),
+                                scale.data_ptr<float>(), N, K,
+                                current_stream()));
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -397,6 +480,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("norm_weight") = pybind11::none(),
           pybind11::arg("eps") = 1e-5,
           pybind11::arg("out") = pybind11::none());
+    m.def("gemm_w8", &gemm_w8,
+          "W8A16 skinny decode GEMM y = x @ (scale * q).T (1 <= M <= 256), q "
+          "the fragment-major fp8 e4m3 twin; with residual/norm_weight/out "
+          "the split-K reduce also adds the residual and RMS-normalizes",
+          pybind11::arg("y"), pybind11::arg("x"), pybind11::arg("q_frag"),
+          pybind11::arg("scale"), pybind11::arg("workspace"),
+          pybind11::arg("nsk"),
+          pybind11::arg("residual") = pybind11::none(),
+          pybind11::arg("norm_weight") = pybind11::none(),
+          pybind11::arg("eps") = 1e-5,
+          pybind11::arg("out") = pybind11::none());
+    m.def("dequant_w8", &dequant_w8,
+          "fragment-major fp8 twin + scale -> row-major bf16 [N, K]");
 
     pybind11::class_<BlockAllocator>(m, "BlockAllocator")
         .def(pybind11::init<int64_t>())

@@ -100,6 +100,71 @@ def fp8_dequantize_rows(bits: torch.Tensor, scale: torch.Tensor) -> torch.Tensor
     return bits.view(torch.float8_e4m3fn).float() * scale.unsqueeze(-1).float()
 
 
+def fp8_quantize_weight(w: torch.Tensor):
+    """Weight quantisation to e4m3fn, one scale per output channel:
+    w [N, K] -> (bits uint8 [N, K], scale fp32 [N]).
+
+    The scale is the smallest power of two s with amax/s <= 448 (an
+    all-zero row gets 1). e4m3 is a floating format, so a power-of-two
+    scale costs no relative precision, and bits*scale is exactly
+    representable in bf16 (3 mantissa bits, exponent shift only)."""
+    wf = w.float()
+    amax = wf.abs().amax(dim=-1)
+    # amax/448 = m * 2^e with m in [0.5, 1): the smallest power of two not
+    # below it is 2^(e-1) when m == 0.5 exactly, else 2^e
+    m, e = torch.frexp(amax / FP8_MAX)
+    e = torch.where(m == 0.5, e - 1, e)
+    scale = torch.where(
+        amax > 0, torch.ldexp(torch.ones_like(amax), e), torch.ones_like(amax)
+    )
+    # the clamp only guards the rounding of amax/448 itself (torch's e4m3fn
+    # cast does not saturate)
+    q = (wf / scale.unsqueeze(-1)).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+    return q.view(torch.uint8), scale
+
+
+def fp8_dequantize_weight(
+    q: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype = torch.bfloat16
+) -> torch.Tensor:
+    """bits [N, K] * scale [N] -> [N, K]; exact for bf16 (and wider)."""
+    return (q.view(torch.float8_e4m3fn).float() * scale.float().unsqueeze(-1)).to(dtype)
+
+
+def swizzle_weight_frag_fp8(q: torch.Tensor) -> torch.Tensor:
+    """bits [N, K] -> fragment-major [K/64, N/16, 64, 16] for gemm_w8.
+
+    [k64][n16][lane][j] = q[n16*16 + (lane&15)][k64*64 + (j>>3)*32 +
+    (lane>>4)*8 + (j&7)]: each 1 KiB row is one wave's
+    mfma_f32_16x16x32_bf16 B-fragments for two consecutive k-steps, one
+    16-byte load per lane (the swizzle_weight_frag fragment convention)."""
+    N, K = q.shape
+    assert K % 64 == 0 and N % 64 == 0
+    # k = k64*64 + h*32 + g*8 + e, n = n16*16 + r; lane = g*16 + r, j = h*8 + e
+    return (
+        q.view(N // 16, 16, K // 64, 2, 4, 8)
+        .permute(2, 0, 4, 1, 3, 5)
+        .reshape(K // 64, N // 16, 64, 16)
+        .contiguous()
+    )
+
+
+def unswizzle_weight_frag_fp8(q_frag: torch.Tensor) -> torch.Tensor:
+    """Inverse of swizzle_weight_frag_fp8: [K/64, N/16, 64, 16] -> [N, K]."""
+    k64, n16 = q_frag.shape[0], q_frag.shape[1]
+    return (
+        q_frag.view(k64, n16, 4, 16, 2, 8)
+        .permute(1, 3, 0, 4, 2, 5)
+        .reshape(n16 * 16, k64 * 64)
+        .contiguous()
+    )
+
+
+def linear_w8(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """y = x @ (scale * q).T with q the row-major e4m3 bits [N, K]."""
+    w = fp8_dequantize_weight(q, scale, torch.float32)
+    return (x.float() @ w.T).to(x.dtype)
+
+
 def kv_cache_write(
     k: torch.Tensor,
     v: torch.Tensor,

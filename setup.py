@@ -25,6 +25,7 @@ sources = [
     os.path.join(CSRC, "sampling.hip"),
     os.path.join(CSRC, "gemm_skinny.hip"),
     os.path.join(CSRC, "gemm_m256.hip"),
+    os.path.join(CSRC, "gemm_w8.hip"),
 ]
 
 setup(
