@@ -215,21 +215,35 @@ _SPLIT_SPAN = 2048  # keep in sync with SPLIT_SPAN in attention_decode.hip
 # decode-attention geometry: 2 = shared-LDS-chunk / wave-per-head form
 # (coalesced staging, no cross-wave combine); 1 = the round-1 form
 _DECODE_VER = int(os.environ.get("LLMAPI_DECODE_VER", "2"))
-_decode_ws: dict = {}
-_decode_ws_retired: list = []
 
 
-def _decode_scratch(device, n_acc: int, n_ml: int):
-    ws = _decode_ws.get(device.index)
-    if ws is None or ws[0].numel() < n_acc or ws[1].numel() < n_ml:
-        if ws is not None:
-            _decode_ws_retired.append(ws)  # captured graphs may still use it
-        ws = (
-            torch.empty(n_acc, dtype=torch.float32, device=device),
-            torch.empty(n_ml, dtype=torch.float32, device=device),
-        )
-        _decode_ws[device.index] = ws
-    return ws
+class _Scratch:
+    """Grow-only per-device scratch buffer. Kernels fully overwrite what
+    they use, so nothing is zeroed and the address is stable across
+    hipGraph replays; a buffer is never shrunk, and when one has to grow
+    the old one is retired, not freed: a captured graph may still replay
+    into it."""
+
+    def __init__(self, dtype: torch.dtype):
+        self.dtype = dtype
+        self.bufs: dict = {}
+        self.retired: list = []
+
+    def get(self, device, numel: int) -> torch.Tensor:
+        device = torch.device(device)
+        buf = self.bufs.get(device.index)
+        if buf is None or buf.numel() < numel:
+            if buf is not None:
+                self.retired.append(buf)
+            buf = torch.empty(numel, dtype=self.dtype, device=device)
+            self.bufs[device.index] = buf
+        return buf
+
+
+_decode_acc = _Scratch(torch.float32)  # flash-decode partial accumulators
+_decode_ml = _Scratch(torch.float32)   # ... and their (max, sum) pairs
+_slabs = _Scratch(torch.float32)       # split-K fp32 slabs of the decode GEMMs
+_w8_dq = _Scratch(torch.bfloat16)      # bf16 image of an fp8 weight (M > 256)
 
 
 def attention_decode(
@@ -255,9 +269,8 @@ def attention_decode(
         if B * k_cache.shape[1] < 192 and max_ctx > _SPLIT_SPAN:
             nsplit = min(8, -(-max_ctx // _SPLIT_SPAN))
         if nsplit > 1:
-            pa, pm = _decode_scratch(
-                q.device, B * Hq * nsplit * q.shape[2], B * Hq * nsplit * 2
-            )
+            pa = _decode_acc.get(q.device, B * Hq * nsplit * q.shape[2])
+            pm = _decode_ml.get(q.device, B * Hq * nsplit * 2)
             # measured: the v1 geometry wins once the flash-decode split
             # path engages (small-batch long-context), v2 everywhere else
             _native().attention_decode(
@@ -285,34 +298,48 @@ def attention_decode(
 # latency regime only.
 _SKINNY_MAX_M = int(os.environ.get("SKINNY_GEMM_MAX_M", "16"))
 _SKINNY_MAX_N = 28672
-# per-device split-K fp32 slab scratch — each workgroup fully overwrites
-# its slab stripe, so no zeroing is needed and the address is stable
-# across hipGraph replays.
-_skinny_ws: dict = {}
+
+
+def _stream_nsk(N: int, K: int, kstep: int) -> int:
+    """Split-K factor of the streaming kernels (csrc/gemm_stream.h), whose
+    pipeline steps are kstep deep: target exactly 256 workgroups (one
+    8-wave WG fills a CU; extra WGs only queue) — more splits just multiply
+    the fp32 slab traffic, which at the old 512-WG target added ~60% to the
+    weight stream and halved in-engine decode throughput. A slice keeps at
+    least 8 steps."""
+    tiles = N // 64
+    nsk = max(1, -(-256 // tiles))
+    return min(nsk, max(1, (K // kstep) // 8), 8)
 
 
 def _skinny_nsk(N: int, K: int) -> int:
-    """Split-K factor: target exactly 256 workgroups (one 8-wave WG fills
-    a CU; extra WGs only queue) — more splits just multiply the fp32 slab
-    traffic, which at the old 512-WG target added ~60% to the weight
-    stream and halved in-engine decode throughput."""
-    tiles = N // 64
-    nsk = max(1, -(-256 // tiles))
-    nsk = min(nsk, max(1, (K // 32) // 8), 8)
-    return nsk
+    return _stream_nsk(N, K, 32)
 
 
-_skinny_ws_retired: list = []  # keep old slabs alive for captured graphs
+def _w8_nsk(N: int, K: int) -> int:
+    return _stream_nsk(N, K, 64)
 
 
-def _skinny_scratch(device, numel: int):
-    ws = _skinny_ws.get(device.index)
-    if ws is None or ws.numel() < numel:
-        if ws is not None:
-            _skinny_ws_retired.append(ws)  # a hipGraph may still replay into it
-        ws = torch.empty(numel, dtype=torch.float32, device=device)
-        _skinny_ws[device.index] = ws
-    return ws
+def _gemm_skinny(x: torch.Tensor, w: torch.Tensor, swizzled: bool) -> torch.Tensor:
+    """The bf16 streaming kernel on w [N, K], or on its k-major twin."""
+    M, K = x.shape
+    N = w.shape[1] if swizzled else w.shape[0]
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    nsk = _skinny_nsk(N, K)
+    ws = _slabs.get(x.device, nsk * M * N) if nsk > 1 else None
+    _native().gemm_skinny(y, x, w, ws, nsk, swizzled)
+    return y
+
+
+def _splitk_norm(launch, x: torch.Tensor, N: int, nsk: int, residual, norm_w, eps):
+    """Run a split-K GEMM whose slab reduction also adds the residual and
+    RMS-normalizes. launch(y, ws, *tail) is the binding call; y is not
+    written on this path, so `out` stands in for its shape check."""
+    M = x.shape[0]
+    out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    ws = _slabs.get(x.device, nsk * M * N)
+    launch(out, ws, residual, norm_w, float(eps), out)
+    return out, residual
 
 
 def swizzle_weight(w: torch.Tensor) -> torch.Tensor:
@@ -433,7 +460,7 @@ def gemm_m256(
         if pipe in (1, 4, 5) and nf != 4:
             pipe = 0
     y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    ws = _skinny_scratch(x.device, nsk * M * N) if nsk > 1 else None
+    ws = _slabs.get(x.device, nsk * M * N) if nsk > 1 else None
     _native().gemm_m256(y, x, w_frag, ws, nsk, nf, variant, pipe, 0)
     return y
 
@@ -453,42 +480,58 @@ def gemm_m256_rmsnorm_residual(
     the norm fused into the split-K slab reduction of gemm_m256 (one kernel
     instead of reduce + norm; the bf16 y never touches HBM). residual is
     updated in place, bit-identical to the unfused pair. Needs nsk > 1."""
-    M, K = x.shape
-    N = w_frag.shape[1] * 16
     if nsk < 2:
         raise ValueError("fused reduce+norm needs split-K slabs (nsk > 1)")
-    out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    ws = _skinny_scratch(x.device, nsk * M * N)
-    # y is not written on the fused path; `out` stands in for its shape check
-    _native().gemm_m256(
-        out, x, w_frag, ws, nsk, nf, variant, pipe, 0,
-        residual, norm_w, float(eps), out,
+    return _splitk_norm(
+        lambda y, ws, *tail: _native().gemm_m256(
+            y, x, w_frag, ws, nsk, nf, variant, pipe, 0, *tail
+        ),
+        x, w_frag.shape[1] * 16, nsk, residual, norm_w, eps,
     )
-    return out, residual
 
 
-def _m256_route(
-    x: torch.Tensor, w: torch.Tensor, w_swz: Optional[torch.Tensor]
-) -> Optional[dict]:
-    """gemm_m256 kwargs when linear() sends this call to the macro-tile
-    kernel, else None (library, skinny kernel or CPU)."""
-    M = x.shape[0]
+def _linear_route(
+    M: int, N: int, K: int, twin: Optional[str], eligible: bool = True
+) -> Tuple[str, dict]:
+    """Where linear() sends a call: (route, kwargs) with route one of
+    "m256" (gemm_m256 kwargs), "skinny" ({"swizzled": bool}) or "library".
+    twin is the layout of the pre-swizzled weight copy: "frag"
+    (fragment-major), "kmajor" (legacy) or None. eligible says the tensors
+    suit the custom kernels at all: x a contiguous 2-D bf16 GPU tensor, w
+    contiguous bf16."""
     if not (
+        eligible
+        and M > 0
+        and N % 64 == 0
+        and N <= _SKINNY_MAX_N
+        and K % 32 == 0
+    ):
+        return "library", {}
+    if twin == "frag" and 8 < M <= 256 and K % 64 == 0:
+        # the measured table decides; a shape it leaves out is the
+        # library's, even where M <= 16 would fit the skinny kernel
+        cfg = _m256_config(M, N, K)
+        return ("m256", cfg) if cfg is not None else ("library", {})
+    if twin == "kmajor" and M <= _SKINNY_SWZ_MAX_M:
+        return "skinny", {"swizzled": True}
+    if M <= _SKINNY_MAX_M:
+        return "skinny", {"swizzled": False}
+    return "library", {}
+
+
+def _route_of(
+    x: torch.Tensor, w: torch.Tensor, w_swz: Optional[torch.Tensor]
+) -> Tuple[str, dict]:
+    twin = None if w_swz is None else {4: "frag", 3: "kmajor"}.get(w_swz.dim())
+    eligible = (
         x.is_cuda
         and x.dim() == 2
         and x.dtype == torch.bfloat16
         and w.dtype == torch.bfloat16
-        and w.shape[0] % 64 == 0
-        and w.shape[0] <= _SKINNY_MAX_N
-        and w.shape[1] % 64 == 0
         and x.is_contiguous()
         and w.is_contiguous()
-        and w_swz is not None
-        and w_swz.dim() == 4
-        and 8 < M <= 256
-    ):
-        return None
-    return _m256_config(M, w.shape[0], w.shape[1])
+    )
+    return _linear_route(x.shape[0], w.shape[0], w.shape[1], twin, eligible)
 
 
 def linear_rmsnorm_residual(
@@ -503,9 +546,9 @@ def linear_rmsnorm_residual(
     if not x.is_cuda:
         return reference.linear_rmsnorm_residual(x, w, residual, norm_w, eps)
     if not os.environ.get("LLMAPI_NO_DECODE_FUSION"):
-        cfg = _m256_route(x, w, w_swz)
+        route, cfg = _route_of(x, w, w_swz)
         if (
-            cfg is not None
+            route == "m256"
             and cfg["nsk"] > 1
             and _reduce_norm_covers(w.shape[0])
             and residual.is_contiguous()
@@ -584,71 +627,23 @@ def linear(
     weight twin exists (models/llama.py builds them), through the
     streaming skinny kernel (csrc/gemm_skinny.hip) in the latency regime
     otherwise; everything else through the TunableOp-tuned library GEMMs."""
-    M = x.shape[0]
-    if (
-        x.is_cuda
-        and x.dtype == torch.bfloat16
-        and w.dtype == torch.bfloat16
-        and 0 < M
-        and w.shape[0] % 64 == 0
-        and w.shape[0] <= _SKINNY_MAX_N
-        and w.shape[1] % 32 == 0
-        and x.is_contiguous()
-        and w.is_contiguous()
-    ):
-        N, K = w.shape
-        if (
-            w_swz is not None
-            and w_swz.dim() == 4
-            and 8 < M <= 256
-            and K % 64 == 0
-        ):
-            cfg = _m256_config(M, N, K)
-            if cfg is not None:
-                return gemm_m256(x, w_swz, **cfg)
-            # fall through to library (measured faster for this shape)
-            return torch.nn.functional.linear(x, w)
-        if w_swz is not None and w_swz.dim() == 3 and M <= _SKINNY_SWZ_MAX_M:
-            # legacy k-major twin -> streaming skinny kernel
-            y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-            nsk = _skinny_nsk(N, K)
-            ws = _skinny_scratch(x.device, nsk * M * N) if nsk > 1 else None
-            _native().gemm_skinny(y, x, w_swz, ws, nsk, True)
-            return y
-        if M <= _SKINNY_MAX_M:
-            y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-            nsk = _skinny_nsk(N, K)
-            ws = _skinny_scratch(x.device, nsk * M * N) if nsk > 1 else None
-            _native().gemm_skinny(y, x, w, ws, nsk, False)
-            return y
+    route, kw = _route_of(x, w, w_swz)
+    if route == "m256":
+        return gemm_m256(x, w_swz, **kw)
+    if route == "skinny":
+        return _gemm_skinny(x, w_swz if kw["swizzled"] else w, kw["swizzled"])
     return torch.nn.functional.linear(x, w)
 
 
 # ---- fp8 (e4m3) weights: W8A16 decode GEMM (csrc/gemm_w8.hip) ----
-_W8_MAX_M = 256  # keep in sync with W8_MAX_M in gemm_w8.hip
-# per-device bf16 buffer the M > 256 route dequantises into; reserved once
-# at model init (w8_reserve_dequant) so captured graphs never see it move
-_w8_dq: dict = {}
-_w8_dq_retired: list = []
-
-
-def _w8_nsk(N: int, K: int) -> int:
-    """The _skinny_nsk rule at the kernel's k64 step granularity."""
-    tiles = N // 64
-    nsk = max(1, -(-256 // tiles))
-    return min(nsk, max(1, (K // 64) // 8), 8)
+_W8_MAX_M = 256  # keep in sync with GS_MAX_M in gemm_stream.h
 
 
 def w8_reserve_dequant(device, numel: int) -> torch.Tensor:
-    """Make the per-device dequantisation buffer hold at least numel bf16."""
-    device = torch.device(device)
-    buf = _w8_dq.get(device.index)
-    if buf is None or buf.numel() < numel:
-        if buf is not None:
-            _w8_dq_retired.append(buf)  # a hipGraph may still replay into it
-        buf = torch.empty(numel, dtype=torch.bfloat16, device=device)
-        _w8_dq[device.index] = buf
-    return buf
+    """Make the per-device buffer the M > 256 route dequantises into hold at
+    least numel bf16. Reserved once at model init, so captured graphs never
+    see it move."""
+    return _w8_dq.get(device, numel)
 
 
 def dequant_w8(
@@ -700,7 +695,7 @@ def linear_w8(
     if nsk is None:
         nsk = _w8_nsk(N, K)
     y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    ws = _skinny_scratch(x.device, nsk * M * N) if nsk > 1 else None
+    ws = _slabs.get(x.device, nsk * M * N) if nsk > 1 else None
     _native().gemm_w8(y, x, q_frag, scale, ws, nsk)
     return y
 
@@ -726,13 +721,12 @@ def linear_w8_rmsnorm_residual(
             and _reduce_norm_covers(N)
             and residual.is_contiguous()
         ):
-            out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-            ws = _skinny_scratch(x.device, k * M * N)
-            # y is not written on the fused path; `out` stands in for it
-            _native().gemm_w8(
-                out, x, q_frag, scale, ws, k, residual, norm_w, float(eps), out
+            return _splitk_norm(
+                lambda y, ws, *tail: _native().gemm_w8(
+                    y, x, q_frag, scale, ws, k, *tail
+                ),
+                x, N, k, residual, norm_w, eps,
             )
-            return out, residual
     return rmsnorm_residual(linear_w8(x, q_frag, scale, nsk), residual, norm_w, eps)
 
 

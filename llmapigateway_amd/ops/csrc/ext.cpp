@@ -9,6 +9,7 @@
 
 #include <vector>
 
+#include "gemm_launch.h"
 #include "kv_manager.cpp"
 
 extern "C" {
@@ -22,10 +23,6 @@ hipError_t launch_attention_decode(void*, const void*, const void*, const void*,
 hipError_t launch_attention_prefill(void*, const void*, const void*, const void*, const int*, const int*, const int*, int, float, int, int, int, int64_t, int64_t, int64_t, const void*, const void*, const float*, const float*, const int*, const int*, int, int, hipStream_t);
 hipError_t launch_sample(int64_t*, const float*, const float*, const float*, float*, int*, int, int, hipStream_t);
 hipError_t launch_topk_topp_filter(float*, const float*, const int*, int, int, hipStream_t);
-hipError_t launch_gemm_skinny(void*, float*, const void*, const void*, int, int, int, int, int, hipStream_t);
-hipError_t launch_gemm_m256(void*, float*, const void*, const void*, int, int, int, int, int, int, int, int, void*, const void*, float, void*, hipStream_t);
-hipError_t launch_gemm_w8(void*, float*, const void*, const void*, const float*, int, int, int, int, void*, const void*, float, void*, hipStream_t);
-hipError_t launch_dequant_w8(void*, const void*, const float*, int, int, hipStream_t);
 }
 
 namespace {
@@ -283,6 +280,54 @@ void topk_topp_filter(torch::Tensor logits, torch::Tensor topp, torch::Tensor to
                                       current_stream()));
 }
 
+// optional fp32 split-K slab workspace: nullptr when absent
+float* workspace_ptr(const c10::optional<torch::Tensor>& ws, int64_t numel) {
+    if (!ws.has_value() || !ws->defined()) return nullptr;
+    TORCH_CHECK(ws->is_cuda() && ws->scalar_type() == torch::kFloat32 &&
+                ws->is_contiguous() && ws->numel() >= numel,
+                "workspace must be fp32 with >= nsk*M*N elements");
+    return ws->data_ptr<float>();
+}
+
+// The fused split-K reduce + residual add + RMSNorm tail: residual is
+// updated in place, out receives the normed rows and y is not written.
+// All three tensors or none; all pointers null when absent.
+struct NormTail {
+    void* residual = nullptr;
+    void* norm_weight = nullptr;
+    void* out = nullptr;
+};
+
+NormTail norm_tail(const c10::optional<torch::Tensor>& residual,
+                   const c10::optional<torch::Tensor>& norm_weight,
+                   const c10::optional<torch::Tensor>& out, int M, int N,
+                   int64_t nsk, const float* ws) {
+    NormTail t;
+    if (!residual.has_value() && !norm_weight.has_value() && !out.has_value())
+        return t;
+    TORCH_CHECK(residual.has_value() && norm_weight.has_value() &&
+                out.has_value(),
+                "residual, norm_weight and out go together");
+    TORCH_CHECK(nsk > 1 && ws != nullptr,
+                "fused reduce+norm needs split-K (nsk > 1) slabs");
+    check_bf16(*residual, "residual");
+    check_bf16(*norm_weight, "norm_weight");
+    check_bf16(*out, "out");
+    TORCH_CHECK(residual->is_contiguous() && out->is_contiguous() &&
+                norm_weight->is_contiguous());
+    TORCH_CHECK(residual->dim() == 2 && residual->size(0) == M &&
+                residual->size(1) == N && out->dim() == 2 &&
+                out->size(0) == M && out->size(1) == N &&
+                norm_weight->numel() == N,
+                "residual/out must be [M, N], norm_weight [N]");
+    TORCH_CHECK(gemm_reduce_rmsnorm_covers(N),
+                "fused reduce+norm covers N % 512 == 0, N <= 8192");
+    t.residual = residual->data_ptr();
+    t.norm_weight = norm_weight->data_ptr();
+    t.out = out->data_ptr();
+    return t;
+}
+
 void gemm_skinny(torch::Tensor y, torch::Tensor x, torch::Tensor w,
                  c10::optional<torch::Tensor> workspace, int64_t nsk,
                  bool swizzled) {
@@ -301,13 +346,7 @@ void gemm_skinny(torch::Tensor y, torch::Tensor x, torch::Tensor w,
         N = w.size(0);
     }
     TORCH_CHECK(y.size(0) == M && y.size(1) == N);
-    float* ws = nullptr;
-    if (workspace.has_value() && workspace->defined()) {
-        TORCH_CHECK(workspace->scalar_type() == torch::kFloat32 &&
-                    workspace->numel() >= nsk * (int64_t)M * N,
-                    "workspace must be fp32 with >= nsk*M*N elements");
-        ws = workspace->data_ptr<float>();
-    }
+    float* ws = workspace_ptr(workspace, nsk * (int64_t)M * N);
     CHECK_HIP(launch_gemm_skinny(y.data_ptr(), ws, x.data_ptr(), w.data_ptr(),
                                  M, N, K, (int)nsk, swizzled ? 1 : 0,
                                  current_stream()));
@@ -333,42 +372,16 @@ void gemm_m256(torch::Tensor y, torch::Tensor x, torch::Tensor w_frag,
     // fused swiglu epilogue: w_frag is the block-16 interleaved gate/up
     // twin and y holds silu(gate)*up, half the columns
     TORCH_CHECK(y.size(0) == M && y.size(1) == (swiglu ? N / 2 : N));
-    float* ws = nullptr;
-    if (workspace.has_value() && workspace->defined()) {
-        TORCH_CHECK(workspace->scalar_type() == torch::kFloat32 &&
-                    workspace->numel() >= nsk * (int64_t)M * N,
-                    "workspace must be fp32 with >= nsk*M*N elements");
-        ws = workspace->data_ptr<float>();
-    }
-    // fused split-K reduce + residual add + RMSNorm: residual is updated
-    // in place, out receives the normed rows, y is not written
-    void *res_p = nullptr, *nw_p = nullptr, *out_p = nullptr;
-    if (residual.has_value() || norm_weight.has_value() || out.has_value()) {
-        TORCH_CHECK(residual.has_value() && norm_weight.has_value() &&
-                    out.has_value(),
-                    "residual, norm_weight and out go together");
-        TORCH_CHECK(nsk > 1 && !swiglu && ws != nullptr,
-                    "fused reduce+norm needs split-K (nsk > 1) slabs");
-        check_bf16(*residual, "residual");
-        check_bf16(*norm_weight, "norm_weight");
-        check_bf16(*out, "out");
-        TORCH_CHECK(residual->is_contiguous() && out->is_contiguous() &&
-                    norm_weight->is_contiguous());
-        TORCH_CHECK(residual->dim() == 2 && residual->size(0) == M &&
-                    residual->size(1) == N && out->dim() == 2 &&
-                    out->size(0) == M && out->size(1) == N &&
-                    norm_weight->numel() == N,
-                    "residual/out must be [M, N], norm_weight [N]");
-        TORCH_CHECK(N % 512 == 0 && N <= 8192,
-                    "fused reduce+norm covers N % 512 == 0, N <= 8192");
-        res_p = residual->data_ptr();
-        nw_p = norm_weight->data_ptr();
-        out_p = out->data_ptr();
-    }
+    float* ws = workspace_ptr(workspace, nsk * (int64_t)M * N);
+    TORCH_CHECK(!(swiglu && (residual.has_value() || norm_weight.has_value() ||
+                             out.has_value())),
+                "fused reduce+norm needs split-K (nsk > 1) slabs");
+    const NormTail t = norm_tail(residual, norm_weight, out, M, N, nsk, ws);
     CHECK_HIP(launch_gemm_m256(y.data_ptr(), ws, x.data_ptr(),
                                w_frag.data_ptr(), M, N, K, (int)nsk, (int)nf,
-                               (int)variant, (int)pipe, (int)swiglu, res_p,
-                               nw_p, (float)eps, out_p, current_stream()));
+                               (int)variant, (int)pipe, (int)swiglu,
+                               t.residual, t.norm_weight, (float)eps, t.out,
+                               current_stream()));
 }
 
 // fragment-major fp8 weight twin [K/64, N/16, 64, 16] (uint8 e4m3 bits) and
@@ -404,41 +417,13 @@ void gemm_w8(torch::Tensor y, torch::Tensor x, torch::Tensor q_frag,
     const int N = check_w8(q_frag, scale, K);
     TORCH_CHECK(y.size(0) == M && y.size(1) == N);
     TORCH_CHECK(nsk >= 1 && nsk <= K / 64, "nsk must be in [1, K/64]");
-    float* ws = nullptr;
-    if (workspace.has_value() && workspace->defined()) {
-        TORCH_CHECK(workspace->is_cuda() &&
-                    workspace->scalar_type() == torch::kFloat32 &&
-                    workspace->is_contiguous() &&
-                    workspace->numel() >= nsk * (int64_t)M * N,
-                    "workspace must be fp32 with >= nsk*M*N elements");
-        ws = workspace->data_ptr<float>();
-    }
+    float* ws = workspace_ptr(workspace, nsk * (int64_t)M * N);
     TORCH_CHECK(nsk == 1 || ws != nullptr, "split-K needs a workspace");
-    void *res_p = nullptr, *nw_p = nullptr, *out_p = nullptr;
-    if (residual.has_value() || norm_weight.has_value() || out.has_value()) {
-        TORCH_CHECK(residual.has_value() && norm_weight.has_value() &&
-                    out.has_value(),
-                    "residual, norm_weight and out go together");
-        TORCH_CHECK(nsk > 1, "fused reduce+norm needs split-K (nsk > 1) slabs");
-        check_bf16(*residual, "residual");
-        check_bf16(*norm_weight, "norm_weight");
-        check_bf16(*out, "out");
-        TORCH_CHECK(residual->is_contiguous() && out->is_contiguous() &&
-                    norm_weight->is_contiguous());
-        TORCH_CHECK(residual->dim() == 2 && residual->size(0) == M &&
-                    residual->size(1) == N && out->dim() == 2 &&
-                    out->size(0) == M && out->size(1) == N &&
-                    norm_weight->numel() == N,
-                    "residual/out must be [M, N], norm_weight [N]");
-        TORCH_CHECK(N % 512 == 0 && N <= 8192,
-                    "fused reduce+norm covers N % 512 == 0, N <= 8192");
-        res_p = residual->data_ptr();
-        nw_p = norm_weight->data_ptr();
-        out_p = out->data_ptr();
-    }
+    const NormTail t = norm_tail(residual, norm_weight, out, M, N, nsk, ws);
     CHECK_HIP(launch_gemm_w8(y.data_ptr(), ws, x.data_ptr(), q_frag.data_ptr(),
-                             scale.data_ptr<float>(), M, N, K, (int)nsk, res_p,
-                             nw_p, (float)eps, out_p, current_stream()));
+                             scale.data_ptr<float>(), M, N, K, (int)nsk,
+                             t.residual, t.norm_weight, (float)eps, t.out,
+                             current_stream()));
 }
 
 void dequant_w8(torch::Tensor out, torch::Tensor q_frag, torch::Tensor scale) {

@@ -33,6 +33,7 @@
 // lm_head remain on the TunableOp-tuned library.
 
 #include "common.h"
+#include "gemm_launch.h"
 
 #define GM_BK 64  // k-depth of one staged tile (2 MFMA k-steps)
 
@@ -682,13 +683,6 @@ __global__ void gemm_m256pc_kernel(
     }
 }
 
-extern "C" hipError_t launch_gemm_reduce(void*, const float*, int64_t, int,
-                                         hipStream_t);  // gemm_skinny.hip
-extern "C" int gemm_reduce_rmsnorm_covers(int N);       // gemm_skinny.hip
-extern "C" hipError_t launch_gemm_reduce_rmsnorm(void*, void*, const float*,
-                                                 const void*, float, int, int,
-                                                 int, hipStream_t);
-
 // nf: 4 (BN=64) or 8 (BN=128). M <= 256; N % (16*nf) == 0; K % 64 == 0.
 // variant: 0 = glds-staged (DMA pipeline, depth per `pipe`),
 //          1 = register-staged T14 (2 buffers, loads one tile ahead),
@@ -726,13 +720,8 @@ extern "C" hipError_t launch_gemm_m256(
         else PC_L(false);
 #undef PC_L
         HIP_CHECK_LAST();
-        if (fuse_norm)
-            return launch_gemm_reduce_rmsnorm(norm_out, residual, workspace,
-                                              norm_weight, eps, M, N, nsk,
-                                              stream);
-        if (nsk > 1)
-            return launch_gemm_reduce(y, workspace, (int64_t)M * N, nsk, stream);
-        return hipSuccess;
+        return launch_splitk_tail(y, workspace, M, N, nsk, residual,
+                                  norm_weight, eps, norm_out, stream);
     }
     if (nf != 4 && nf != 8) return hipErrorInvalidValue;
     if ((N % (16 * nf)) != 0) return hipErrorInvalidValue;
@@ -810,12 +799,6 @@ extern "C" hipError_t launch_gemm_m256(
 #undef GM_L1
 #undef GM_L2
     HIP_CHECK_LAST();
-    if (fuse_norm)
-        return launch_gemm_reduce_rmsnorm(norm_out, residual, workspace,
-                                          norm_weight, eps, M, N, nsk, stream);
-    if (nsk > 1) {
-        const int64_t mn = (int64_t)M * N;  // N % 64 == 0 -> mn % 4 == 0
-        return launch_gemm_reduce(y, workspace, mn, nsk, stream);
-    }
-    return hipSuccess;
+    return launch_splitk_tail(y, workspace, M, N, nsk, residual, norm_weight,
+                              eps, norm_out, stream);
 }

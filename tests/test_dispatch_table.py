@@ -101,3 +101,171 @@ def test_interleaved_fused_matches_reference_math():
     )
     g, u = (x @ w.T).chunk(2, dim=-1)
     assert torch.allclose(fused, F.silu(g) * u, atol=1e-5)
+
+
+# ---- linear() routing, pinned over a grid --------------------------------
+# One row per M in _ROUTE_MS, one column per weight twin (none, k-major,
+# fragment-major). LIB = tuned library, SKN / SWZ = streaming skinny kernel
+# on the plain / k-major weight, a tuple = gemm_m256 (nf, nsk, variant,
+# pipe). Recorded from linear() as it stood before the route became a
+# function of its own (native calls stubbed), so the table is the yardstick
+# and not an echo of _linear_route. (4096, 4128) has K % 64 == 32: the
+# fragment twin cannot serve it and M <= 16 falls to the plain kernel.
+LIB, SKN, SWZ = "LIB", "SKN", "SWZ"
+_ROUTE_MS = (1, 8, 9, 16, 17, 64, 256, 257)
+_ROUTE_TWINS = (None, "kmajor", "frag")
+_ROUTES = {
+    (6144, 4096): [
+        (SKN, SWZ, SKN),  # M=1
+        (SKN, SWZ, SKN),  # M=8
+        (SKN, SWZ, LIB),  # M=9
+        (SKN, SWZ, LIB),  # M=16
+        (LIB, SWZ, LIB),  # M=17
+        (LIB, SWZ, LIB),  # M=64
+        (LIB, SWZ, LIB),  # M=256
+        (LIB, LIB, LIB),  # M=257
+    ],
+    (4096, 4096): [
+        (SKN, SWZ, SKN),  # M=1
+        (SKN, SWZ, SKN),  # M=8
+        (SKN, SWZ, (4, 4, 0, 4)),  # M=9
+        (SKN, SWZ, (4, 4, 0, 4)),  # M=16
+        (LIB, SWZ, (4, 4, 0, 4)),  # M=17
+        (LIB, SWZ, (4, 4, 0, 4)),  # M=64
+        (LIB, SWZ, (4, 4, 0, 4)),  # M=256
+        (LIB, LIB, LIB),  # M=257
+    ],
+    (28672, 4096): [
+        (SKN, SWZ, SKN),  # M=1
+        (SKN, SWZ, SKN),  # M=8
+        (SKN, SWZ, LIB),  # M=9
+        (SKN, SWZ, LIB),  # M=16
+        (LIB, SWZ, LIB),  # M=17
+        (LIB, SWZ, LIB),  # M=64
+        (LIB, SWZ, LIB),  # M=256
+        (LIB, LIB, LIB),  # M=257
+    ],
+    (4096, 14336): [
+        (SKN, SWZ, SKN),  # M=1
+        (SKN, SWZ, SKN),  # M=8
+        (SKN, SWZ, (8, 8, 0, 0)),  # M=9
+        (SKN, SWZ, (8, 8, 0, 0)),  # M=16
+        (LIB, SWZ, (8, 8, 0, 0)),  # M=17
+        (LIB, SWZ, (8, 8, 0, 0)),  # M=64
+        (LIB, SWZ, (8, 8, 0, 0)),  # M=256
+        (LIB, LIB, LIB),  # M=257
+    ],
+    (10240, 8192): [
+        (SKN, SWZ, SKN),  # M=1
+        (SKN, SWZ, SKN),  # M=8
+        (SKN, SWZ, LIB),  # M=9
+        (SKN, SWZ, LIB),  # M=16
+        (LIB, SWZ, LIB),  # M=17
+        (LIB, SWZ, LIB),  # M=64
+        (LIB, SWZ, LIB),  # M=256
+        (LIB, LIB, LIB),  # M=257
+    ],
+    (8192, 8192): [
+        (SKN, SWZ, SKN),  # M=1
+        (SKN, SWZ, SKN),  # M=8
+        (SKN, SWZ, (8, 4, 0, 0)),  # M=9
+        (SKN, SWZ, (8, 4, 0, 0)),  # M=16
+        (LIB, SWZ, (8, 4, 0, 0)),  # M=17
+        (LIB, SWZ, (8, 4, 0, 0)),  # M=64
+        (LIB, SWZ, (8, 4, 0, 0)),  # M=256
+        (LIB, LIB, LIB),  # M=257
+    ],
+    (57344, 8192): [
+        (LIB, LIB, LIB),  # M=1
+        (LIB, LIB, LIB),  # M=8
+        (LIB, LIB, LIB),  # M=9
+        (LIB, LIB, LIB),  # M=16
+        (LIB, LIB, LIB),  # M=17
+        (LIB, LIB, LIB),  # M=64
+        (LIB, LIB, LIB),  # M=256
+        (LIB, LIB, LIB),  # M=257
+    ],
+    (8192, 28672): [
+        (SKN, SWZ, SKN),  # M=1
+        (SKN, SWZ, SKN),  # M=8
+        (SKN, SWZ, (8, 4, 1, 0)),  # M=9
+        (SKN, SWZ, (8, 4, 1, 0)),  # M=16
+        (LIB, SWZ, (8, 4, 1, 0)),  # M=17
+        (LIB, SWZ, (8, 4, 1, 0)),  # M=64
+        (LIB, SWZ, (8, 4, 1, 0)),  # M=256
+        (LIB, LIB, LIB),  # M=257
+    ],
+    (1536, 4096): [
+        (SKN, SWZ, SKN),  # M=1
+        (SKN, SWZ, SKN),  # M=8
+        (SKN, SWZ, LIB),  # M=9
+        (SKN, SWZ, LIB),  # M=16
+        (LIB, SWZ, LIB),  # M=17
+        (LIB, SWZ, LIB),  # M=64
+        (LIB, SWZ, LIB),  # M=256
+        (LIB, LIB, LIB),  # M=257
+    ],
+    (4096, 1024): [
+        (SKN, SWZ, SKN),  # M=1
+        (SKN, SWZ, SKN),  # M=8
+        (SKN, SWZ, (4, 1, 1, 0)),  # M=9
+        (SKN, SWZ, (4, 1, 1, 0)),  # M=16
+        (LIB, SWZ, (4, 1, 1, 0)),  # M=17
+        (LIB, SWZ, (4, 1, 1, 0)),  # M=64
+        (LIB, SWZ, (4, 1, 1, 0)),  # M=256
+        (LIB, LIB, LIB),  # M=257
+    ],
+    (7168, 4096): [
+        (SKN, SWZ, SKN),  # M=1
+        (SKN, SWZ, SKN),  # M=8
+        (SKN, SWZ, (4, 3, 0, 4)),  # M=9
+        (SKN, SWZ, (4, 3, 0, 4)),  # M=16
+        (LIB, SWZ, (4, 3, 0, 4)),  # M=17
+        (LIB, SWZ, (4, 3, 0, 4)),  # M=64
+        (LIB, SWZ, (4, 3, 0, 4)),  # M=256
+        (LIB, LIB, LIB),  # M=257
+    ],
+    (4096, 3584): [
+        (SKN, SWZ, SKN),  # M=1
+        (SKN, SWZ, SKN),  # M=8
+        (SKN, SWZ, (4, 4, 0, 4)),  # M=9
+        (SKN, SWZ, (4, 4, 0, 4)),  # M=16
+        (LIB, SWZ, (4, 4, 0, 4)),  # M=17
+        (LIB, SWZ, (4, 4, 0, 4)),  # M=64
+        (LIB, SWZ, (4, 4, 0, 4)),  # M=256
+        (LIB, LIB, LIB),  # M=257
+    ],
+    (4096, 4128): [
+        (SKN, SWZ, SKN),  # M=1
+        (SKN, SWZ, SKN),  # M=8
+        (SKN, SWZ, SKN),  # M=9
+        (SKN, SWZ, SKN),  # M=16
+        (LIB, SWZ, LIB),  # M=17
+        (LIB, SWZ, LIB),  # M=64
+        (LIB, SWZ, LIB),  # M=256
+        (LIB, LIB, LIB),  # M=257
+    ],
+}
+
+
+def _encode(route, kw):
+    if route == "library":
+        assert kw == {}
+        return LIB
+    if route == "skinny":
+        assert set(kw) == {"swizzled"}
+        return SWZ if kw["swizzled"] else SKN
+    assert route == "m256" and set(kw) == {"nf", "nsk", "variant", "pipe"}
+    return (kw["nf"], kw["nsk"], kw["variant"], kw["pipe"])
+
+
+@pytest.mark.parametrize("N,K", sorted(_ROUTES))
+def test_linear_route_grid(N, K):
+    from llmapigateway_amd.ops import _linear_route
+
+    for M, want in zip(_ROUTE_MS, _ROUTES[(N, K)]):
+        got = tuple(_encode(*_linear_route(M, N, K, t)) for t in _ROUTE_TWINS)
+        assert got == want, (M, N, K, got, want)
+        # tensors the custom kernels cannot take always go to the library
+        for t in _ROUTE_TWINS:
+            assert _linear_route(M, N, K, t, eligible=False) == ("library", {})

@@ -153,6 +153,31 @@ def test_gemm_skinny_guards():
     wscheck("gemm_skinny slab")
 
 
+def test_gemm_skinny_kmajor_guards():
+    M, N, K, nsk = 17, 128, 448, 2
+    x = (torch.randn(M, K, device=DEV) * 0.5).bfloat16()
+    w = (torch.randn(N, K, device=DEV) * 0.02).bfloat16()
+    y, ycheck = guarded((M, N), torch.bfloat16)
+    ws, wscheck = guarded((nsk * M * N,), torch.float32)
+    ops._native().gemm_skinny(y, x, ops.swizzle_weight(w), ws, nsk, True)
+    ycheck("gemm_skinny k-major y")
+    wscheck("gemm_skinny k-major slab")
+
+
+def test_gemm_w8_guards():
+    M, N, K, nsk = 17, 128, 448, 2
+    x = (torch.randn(M, K, device=DEV) * 0.5).bfloat16()
+    w = (torch.randn(N, K) * 0.02).bfloat16()
+    q, s = ops.fp8_quantize_weight(w)
+    y, ycheck = guarded((M, N), torch.bfloat16)
+    ws, wscheck = guarded((nsk * M * N,), torch.float32)
+    ops._native().gemm_w8(
+        y, x, ops.swizzle_weight_frag_fp8(q).to(DEV), s.to(DEV), ws, nsk
+    )
+    ycheck("gemm_w8 y")
+    wscheck("gemm_w8 slab")
+
+
 def test_sampling_guards():
     B, V = 64, 128256
     logits = torch.randn(B, V, device=DEV)
