@@ -674,6 +674,136 @@ def _w8_gpu_check(x: torch.Tensor) -> None:
         )
 
 
+def _w8_m256_default(M: int, N: int, K: int) -> dict:
+    """nf and nsk of the macro-tile fp8 kernel where nothing was measured:
+    nf by gemm_m256's rule (4 when N % 128 != 0), nsk from _m256_nsk."""
+    if N % 128 == 0 and M > 64:
+        nf = 8
+    else:
+        nf = 8 if N // 64 >= 448 else 4
+    if N % (16 * nf) != 0:
+        nf = 4
+    return {"nf": nf, "nsk": _m256_nsk(N, K, nf)}
+
+
+# (N, K) -> {measured M: (nf, nsk) or None}. Cold-cache sweep over nf in
+# {4,8} x nsk in {1,2,4,8} (tools/gemm_w8_bench.py --sweep,
+# profiles/r06_w8_macro.md); each comment is "macro vs streaming" in us,
+# medians of 3 rounds. A cell is None where no macro configuration's
+# three-round range lay wholly below the streaming kernel's.
+_W8_M256_TABLE = {
+    (6144, 4096): {      # llama-3-8b qkv
+        64: (4, 8),      # 17.5 vs 22.3
+        128: (4, 8),     # 20.6 vs 36.6
+        256: (8, 4),     # 29.2 vs 56.8
+    },
+    (4096, 4096): {      # llama-3-8b o
+        64: None,        # best 17.2 vs 13.4
+        128: (4, 8),     # 18.4 vs 20.4
+        256: (4, 4),     # 22.0 vs 28.1
+    },
+    (28672, 4096): {     # llama-3-8b gate_up
+        64: (4, 2),      # 40.3 vs 50.5
+        128: (8, 2),     # 51.6 vs 92.9
+        256: (8, 1),     # 70.5 vs 152.0
+    },
+    (4096, 14336): {     # llama-3-8b down
+        64: None,        # best 31.5 vs 28.1
+        128: (4, 8),     # 33.4 vs 49.3
+        256: (8, 8),     # 47.0 vs 74.1
+    },
+    (10240, 8192): {     # llama-3-70b qkv
+        64: (8, 8),      # 33.3 vs 54.2
+        128: (4, 4),     # 45.0 vs 97.5
+        256: (8, 2),     # 74.3 vs 156.3
+    },
+    (8192, 8192): {      # llama-3-70b o
+        64: (4, 8),      # 27.5 vs 29.5
+        128: (8, 8),     # 34.7 vs 54.1
+        256: (8, 4),     # 51.0 vs 82.6
+    },
+    (57344, 8192): {     # llama-3-70b gate_up
+        64: (4, 1),      # 125.7 vs 199.4
+        128: (8, 1),     # 158.4 vs 368.7
+        256: (8, 1),     # 267.2 vs 600.3
+    },
+    (8192, 28672): {     # llama-3-70b down
+        64: (4, 8),      # 67.1 vs 93.7
+        128: (8, 8),     # 89.6 vs 181.7
+        256: (8, 4),     # 145.4 vs 285.1
+    },
+}
+_W8_M256_MS = (64, 128, 256)  # the batch sizes the sweep measured
+
+
+def _w8_m256_config(M: int, N: int, K: int) -> Optional[dict]:
+    """Measured dispatch table of the macro-tile fp8 kernel
+    (csrc/gemm_w8_m256.hip) against the streaming fp8 kernel. Returns
+    {"nf", "nsk"}, or None to keep the streaming kernel. Only the measured
+    shapes have entries. A measured M takes its own cell; an M between two
+    measured batch sizes takes the upper one's configuration (the kernel
+    runs the same wave count there), and only where the macro kernel won at
+    BOTH ends; below the smallest measured M nothing is assumed."""
+    row = _W8_M256_TABLE.get((N, K))
+    if row is None or not (_W8_M256_MS[0] <= M <= _W8_M256_MS[-1]):
+        return None
+    hi = next(i for i, m in enumerate(_W8_M256_MS) if m >= M)
+    cell = row[_W8_M256_MS[hi]]
+    if cell is None or (M != _W8_M256_MS[hi] and row[_W8_M256_MS[hi - 1]] is None):
+        return None
+    return {"nf": cell[0], "nsk": cell[1]}
+
+
+def _w8_macro_config(M: int, N: int, K: int) -> Optional[dict]:
+    """The macro-tile route of linear_w8 for this call, or None. Opt-in:
+    LLMAPI_W8_MACRO_MIN_M=m (read at call time) sends m <= M <= 256 to
+    gemm_w8_m256 wherever the measured table has an entry."""
+    knob = os.environ.get("LLMAPI_W8_MACRO_MIN_M")
+    if not knob or not (int(knob) <= M <= _W8_MAX_M):
+        return None
+    return _w8_m256_config(M, N, K)
+
+
+def gemm_w8_m256(
+    x: torch.Tensor, q_frag: torch.Tensor, scale: torch.Tensor,
+    nf: Optional[int] = None, nsk: Optional[int] = None,
+) -> torch.Tensor:
+    """y = x @ (scale * q).T on the macro-tile W8A16 kernel
+    (csrc/gemm_w8_m256.hip): the structure of the register-staged gemm_m256
+    with the fp8 twin converted once per workgroup into the LDS tile.
+    M <= 256; nf in {4, 8} is the column-tile width in 16-col fragments."""
+    M, K = x.shape
+    N = q_frag.shape[1] * 16
+    cfg = _w8_m256_default(M, N, K)
+    if nf is None:
+        nf = cfg["nf"]
+    if nsk is None:
+        nsk = cfg["nsk"] if nf == cfg["nf"] else _m256_nsk(N, K, nf)
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    ws = _slabs.get(x.device, nsk * M * N) if nsk > 1 else None
+    _native().gemm_w8_m256(y, x, q_frag, scale, ws, nsk, nf)
+    return y
+
+
+def gemm_w8_m256_rmsnorm_residual(
+    x: torch.Tensor, q_frag: torch.Tensor, scale: torch.Tensor,
+    residual: torch.Tensor, norm_w: torch.Tensor, eps: float, nf: int,
+    nsk: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """rmsnorm_residual(gemm_w8_m256(x, q_frag, scale), residual, norm_w)
+    with the residual add and the norm fused into the split-K slab
+    reduction; residual is updated in place, bit-identical to the unfused
+    pair. Needs nsk > 1."""
+    if nsk < 2:
+        raise ValueError("fused reduce+norm needs split-K slabs (nsk > 1)")
+    return _splitk_norm(
+        lambda y, ws, *tail: _native().gemm_w8_m256(
+            y, x, q_frag, scale, ws, nsk, nf, *tail
+        ),
+        x, q_frag.shape[1] * 16, nsk, residual, norm_w, eps,
+    )
+
+
 def linear_w8(
     x: torch.Tensor, q_frag: torch.Tensor, scale: torch.Tensor,
     nsk: Optional[int] = None,
@@ -682,7 +812,9 @@ def linear_w8(
     (swizzle_weight_frag_fp8) and scale one fp32 per output channel.
     GPU: M <= 256 runs the W8A16 streaming kernel (csrc/gemm_w8.hip),
     larger M dequantises into the per-device bf16 buffer and calls the
-    library GEMM. CPU: the reference."""
+    library GEMM. With LLMAPI_W8_MACRO_MIN_M=m set and no explicit nsk,
+    m <= M <= 256 runs the macro-tile kernel (csrc/gemm_w8_m256.hip) for
+    the shapes _w8_m256_config lists. CPU: the reference."""
     if not x.is_cuda:
         return reference.linear_w8(
             x, reference.unswizzle_weight_frag_fp8(q_frag), scale
@@ -693,6 +825,9 @@ def linear_w8(
     if M > _W8_MAX_M:
         return torch.nn.functional.linear(x, dequant_w8(q_frag, scale))
     if nsk is None:
+        macro = _w8_macro_config(M, N, K)
+        if macro is not None:
+            return gemm_w8_m256(x, q_frag, scale, **macro)
         nsk = _w8_nsk(N, K)
     y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
     ws = _slabs.get(x.device, nsk * M * N) if nsk > 1 else None
@@ -709,11 +844,26 @@ def linear_w8_rmsnorm_residual(
     residual, norm_w, eps). On the split-K kernel route (nsk > 1) with a
     covered row width the residual add and the norm run inside the slab
     reduction; bit-identical to the unfused pair, which every other case
-    runs (LLMAPI_NO_DECODE_FUSION=1 forces it)."""
+    runs (LLMAPI_NO_DECODE_FUSION=1 forces it). The same holds on the
+    macro-tile route (LLMAPI_W8_MACRO_MIN_M, see linear_w8) with that
+    kernel's nsk."""
     if x.is_cuda and not os.environ.get("LLMAPI_NO_DECODE_FUSION"):
         _w8_gpu_check(x)
         M, K = x.shape
         N = q_frag.shape[1] * 16
+        macro = _w8_macro_config(M, N, K) if nsk is None else None
+        if macro is not None:
+            if (
+                macro["nsk"] > 1
+                and _reduce_norm_covers(N)
+                and residual.is_contiguous()
+            ):
+                return gemm_w8_m256_rmsnorm_residual(
+                    x, q_frag, scale, residual, norm_w, eps, **macro
+                )
+            return rmsnorm_residual(
+                gemm_w8_m256(x, q_frag, scale, **macro), residual, norm_w, eps
+            )
         k = _w8_nsk(N, K) if nsk is None else nsk
         if (
             M <= _W8_MAX_M
@@ -776,6 +926,8 @@ __all__ = [
     "unswizzle_weight_frag_fp8",
     "linear_w8",
     "linear_w8_rmsnorm_residual",
+    "gemm_w8_m256",
+    "gemm_w8_m256_rmsnorm_residual",
     "dequant_w8",
     "w8_reserve_dequant",
     "attention_prefill",
