@@ -262,7 +262,9 @@ def attention_decode(
         out = torch.empty_like(q)
         # flash-decode context splits when (B x Hkv) underfills the 256 CUs
         # but the block table allows long contexts; derived only from
-        # capture-stable shapes so hipGraph replays stay valid
+        # capture-stable shapes so hipGraph replays stay valid. Each split
+        # takes _SPLIT_SPAN keys; past 8 * _SPLIT_SPAN positions the count
+        # stays 8 and the launcher widens the span to cover the block table
         B, Hq = q.shape[0], q.shape[1]
         max_ctx = block_tables.shape[1] * k_cache.shape[2]
         nsplit = 1

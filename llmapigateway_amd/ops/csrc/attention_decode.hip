@@ -25,7 +25,8 @@
 #define MAX_G 8
 #define NWAVES 4
 #define DECODE_D 128
-#define SPLIT_SPAN 2048  // context per split (flash-decode partials)
+#define SPLIT_SPAN 2048  // context per split (flash-decode partials); the
+                         // launcher widens it when the splits would not cover
 
 // SPLIT=false: one workgroup per (seq, kv-head) writes out directly.
 // SPLIT=true: grid.z context-splits write un-normalized partials
@@ -54,15 +55,23 @@ __global__ void attention_decode_kernel(
     int64_t q_stride,
     float* __restrict__ part_acc,           // [B, Hq, NSPLIT, D] (SPLIT)
     float* __restrict__ part_ml,            // [B, Hq, NSPLIT, 2] (SPLIT)
-    int nsplit) {
+    int nsplit,
+    int split_span) {                       // keys per split (SPLIT), multiple of 64
     const int seq = blockIdx.x;
     const int kvh = blockIdx.y;
     const int split = SPLIT ? blockIdx.z : 0;
     const int D = DECODE_D;
     const int L = context_lens[seq];
-    if (L <= 0) return;
-    const int span0 = SPLIT ? split * SPLIT_SPAN : 0;
-    if (SPLIT && span0 >= L) {  // idle split: publish an empty partial
+    if (!SPLIT && L <= 0) {  // empty context: the row is defined as zeros
+        uint32_t* o = reinterpret_cast<uint32_t*>(
+            out + (size_t)seq * Hq * DECODE_D + (size_t)kvh * G * DECODE_D);
+        for (int i = threadIdx.x; i < G * DECODE_D / 2; i += blockDim.x) o[i] = 0u;
+        return;
+    }
+    const int span0 = SPLIT ? split * split_span : 0;
+    // idle split (an empty context idles every split): publish an empty
+    // partial, so the combine kernel reads nothing stale and yields zeros
+    if (SPLIT && span0 >= L) {
         const int lane0 = threadIdx.x & (WAVE_SIZE - 1);
         if (threadIdx.x < WAVE_SIZE) {
 #pragma unroll
@@ -75,7 +84,7 @@ __global__ void attention_decode_kernel(
         }
         return;
     }
-    const int span1 = SPLIT ? min(L, span0 + SPLIT_SPAN) : L;
+    const int span1 = SPLIT ? min(L, span0 + split_span) : L;
 
     const int tid = threadIdx.x;
     const int lane = tid & (WAVE_SIZE - 1);
@@ -109,7 +118,7 @@ __global__ void attention_decode_kernel(
         for (int d = 0; d < 4; ++d) acc[g][d] = 0.f;
     }
 
-    const int c0 = span0 / WAVE_SIZE;  // SPLIT_SPAN is a multiple of 64
+    const int c0 = span0 / WAVE_SIZE;  // split_span is a multiple of 64
     const int nchunks = (span1 + WAVE_SIZE - 1) / WAVE_SIZE;
     for (int c = c0 + wave; c < nchunks; c += NWAVES) {
         const int pos = c * WAVE_SIZE + lane;
@@ -323,20 +332,28 @@ __global__ void attention_decode_v2_kernel(
     int64_t q_stride,
     float* __restrict__ part_acc,           // [B, Hq, NSPLIT, D] (SPLIT)
     float* __restrict__ part_ml,            // [B, Hq, NSPLIT, 2] (SPLIT)
-    int nsplit) {
+    int nsplit,
+    int split_span) {                       // keys per split (SPLIT), multiple of 64
     const int seq = blockIdx.x;
     const int kvh = blockIdx.y;
     const int split = SPLIT ? blockIdx.z : 0;
     const int D = DECODE_D;
     const int L = context_lens[seq];
-    if (L <= 0) return;
-    const int span0 = SPLIT ? split * SPLIT_SPAN : 0;
+    if (!SPLIT && L <= 0) {  // empty context: the row is defined as zeros
+        uint32_t* o = reinterpret_cast<uint32_t*>(
+            out + (size_t)seq * Hq * DECODE_D + (size_t)kvh * G * DECODE_D);
+        for (int i = threadIdx.x; i < G * DECODE_D / 2; i += blockDim.x) o[i] = 0u;
+        return;
+    }
+    const int span0 = SPLIT ? split * split_span : 0;
     const int tid = threadIdx.x;
     const int lane = tid & (WAVE_SIZE - 1);
     const int wave = tid >> 6;
     // wave w owns heads {w, w+NWAVES, ...} < G
     constexpr int HPW = (G + NWAVES - 1) / NWAVES;  // heads per wave (max)
-    if (SPLIT && span0 >= L) {  // idle split: publish empty partials
+    // idle split (an empty context idles every split): publish empty
+    // partials, so the combine kernel reads nothing stale and yields zeros
+    if (SPLIT && span0 >= L) {
 #pragma unroll
         for (int hh = 0; hh < HPW; ++hh) {
             const int g = wave + hh * NWAVES;
@@ -347,7 +364,7 @@ __global__ void attention_decode_v2_kernel(
         }
         return;
     }
-    const int span1 = SPLIT ? min(L, span0 + SPLIT_SPAN) : L;
+    const int span1 = SPLIT ? min(L, span0 + split_span) : L;
 
     __shared__ float q_lds[G][DECODE_D];
     __shared__ bf16 k_lds[WAVE_SIZE][DECODE_D];   // 16 KiB (XOR-swizzled)
@@ -798,6 +815,17 @@ extern "C" hipError_t launch_attention_decode(
         return hipErrorInvalidValue;
     const int G = Hq / Hkv;
     const bool fp8 = k_scale != nullptr;
+    // Per-split span: SPLIT_SPAN while nsplit spans of it cover the block
+    // table (the caller caps nsplit at 8, so every table up to 16384
+    // positions), else the table divided evenly, rounded up to whole
+    // 64-key chunks, so that no key past nsplit * SPLIT_SPAN is dropped.
+    // Derived from shapes only (never context_lens): hipGraph-capture-stable.
+    int split_span = SPLIT_SPAN;
+    if (nsplit > 1) {
+        const int64_t max_ctx = (int64_t)max_blocks * block_size;
+        const int64_t even = ((max_ctx + nsplit - 1) / nsplit + 63) / 64 * 64;
+        if (even > SPLIT_SPAN) split_span = (int)even;
+    }
     dim3 grid(B, Hkv, nsplit > 1 ? nsplit : 1);
     dim3 block(NWAVES * WAVE_SIZE);
 #define LAUNCH_G3(GV, SPLIT, FP8V)                                             \
@@ -808,14 +836,14 @@ extern "C" hipError_t launch_attention_decode(
                     (bf16*)out, (const bf16*)q, k_cache, v_cache, k_scale,     \
                     v_scale, block_tables, context_lens, scale, Hq, Hkv,       \
                     block_size, max_blocks, q_stride, part_acc, part_ml,       \
-                    nsplit);                                                   \
+                    nsplit, split_span);                                       \
         else                                                                   \
             attention_decode_kernel<GV, SPLIT, FP8V>                           \
                 <<<grid, block, 0, stream>>>(                                  \
                     (bf16*)out, (const bf16*)q, k_cache, v_cache, k_scale,     \
                     v_scale, block_tables, context_lens, scale, Hq, Hkv,       \
                     block_size, max_blocks, q_stride, part_acc, part_ml,       \
-                    nsplit);                                                   \
+                    nsplit, split_span);                                       \
     } while (0)
 #define LAUNCH_G2(GV, SPLIT)                                                   \
     do {                                                                       \
