@@ -49,7 +49,7 @@ class EngineSpec(BaseModel):
     max_batch_size: Optional[int] = None
     kv_block_size: Optional[int] = None
     kv_dtype: str = "auto"               # "auto" (= compute dtype) | "fp8"
-    weight_dtype: str = "auto"           # "auto" (= compute dtype) | "fp8" (e4m3 projections)
+    weight_dtype: str = "auto"           # "auto" (= compute dtype) | "fp8" (e4m3 projections) | "mxfp4" (e2m1, block-32 scales)
     fail_rate: float = 0.0               # failure injection: P(request fails)
     fail_requests: Optional[int] = None  # failure injection: fail first N requests
 

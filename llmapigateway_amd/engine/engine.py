@@ -194,7 +194,7 @@ class LLMEngine:
             torch.cuda.set_device(self.device)
         if weight_dtype == "auto":
             weight_dtype = os.environ.get("LLMAPI_WEIGHT_DTYPE", "auto")
-        self.weight_dtype = weight_dtype  # "auto" (= compute dtype) | "fp8"
+        self.weight_dtype = weight_dtype  # "auto" (= compute dtype) | "fp8" | "mxfp4"
         self.model = LlamaModel(
             config, device=self.device, dtype=dtype, seed=seed,
             tp_group=tp_group, tp_rank=tp_rank, tp_size=tp_size,

@@ -81,12 +81,17 @@ class LlamaModel:
         full_config: Optional[ModelConfig] = None,
         weight_dtype: str = "auto",
     ):
-        if weight_dtype not in ("auto", "fp8"):
-            raise ValueError(f"weight_dtype must be 'auto' or 'fp8', got {weight_dtype!r}")
+        if weight_dtype not in ("auto", "fp8", "mxfp4"):
+            raise ValueError(
+                f"weight_dtype must be 'auto', 'fp8' or 'mxfp4', got {weight_dtype!r}"
+            )
         # "fp8": the four projections of every layer are held as e4m3 bits
         # (fragment-major, ops.swizzle_weight_frag_fp8) plus one fp32 scale
         # per output channel, and run through ops.linear_w8; embeddings,
-        # lm_head and norms stay in `dtype`
+        # lm_head and norms stay in `dtype`.
+        # "mxfp4": the same four as OCP MXFP4 — e2m1 nibbles plus one e8m0
+        # scale per 32 k of a row (fragment-major,
+        # ops.swizzle_weight_frag_mxfp4) — run through ops.linear_w4
         self.weight_dtype = weight_dtype
         self.config = config
         self.full_config = full_config or config
@@ -131,18 +136,18 @@ class LlamaModel:
         std = 0.02
         out_std = 0.02 / math.sqrt(2 * c.num_layers)
         self.embed = mk(fc.vocab_size, hidden, std)
-        fp8 = self.weight_dtype == "fp8"
+        quant = self.weight_dtype != "auto"
         for _ in range(c.num_layers):
             qkv_full = mk(fc.q_size + 2 * fc.kv_size, hidden, std)
             o_full = mk(hidden, fc.q_size, out_std)
             gu_full = mk(2 * fc.intermediate_size, hidden, std)
             down_full = mk(hidden, fc.intermediate_size, out_std)
-            if fp8:
+            if quant:
                 # quantise the FULL matrices layer by layer (peak memory
-                # stays near the fp8 size), then shard bits and scales: TP=N
-                # stays a pure sharding of the TP=1 quantised model
+                # stays near the quantised size), then shard bits and scales:
+                # TP=N stays a pure sharding of the TP=1 quantised model
                 self.layers.append(
-                    self._fp8_layer(qkv_full, o_full, gu_full, down_full)
+                    self._quant_layer(qkv_full, o_full, gu_full, down_full)
                 )
                 del qkv_full, o_full, gu_full, down_full
                 continue
@@ -163,15 +168,17 @@ class LlamaModel:
         self.final_norm = torch.ones(hidden, dtype=self.dtype, device=self.device)
         self.lm_head = self.embed if c.tie_embeddings else mk(self.full_config.vocab_size, hidden, std)
 
-        if fp8:
+        if quant:
             self._reserve_w8_buffer()
             return  # no bf16 matrices, so no bf16 twins
         self._build_twins()
 
-    def _fp8_layer(self, qkv_full, o_full, gu_full, down_full) -> Dict[str, torch.Tensor]:
-        """One layer's dict in fp8 mode: `<name>_q8` (fragment-major e4m3
-        bits) and `<name>_s8` (fp32 scale per output channel) for the four
-        projections, from the full (unsharded) matrices."""
+    def _quant_layer(self, qkv_full, o_full, gu_full, down_full) -> Dict[str, torch.Tensor]:
+        """One layer's dict in a quantised mode, from the full (unsharded)
+        matrices. fp8: `<name>_q8` (fragment-major e4m3 bits) and `<name>_s8`
+        (fp32 scale per output channel) for the four projections. mxfp4:
+        `<name>_q4` (fragment-major e2m1 nibbles) and `<name>_s4`
+        (fragment-major e8m0 block scales)."""
         from ..parallel.tp import shard_gate_up, shard_qkv, shard_row
 
         fc, tpr, tps = self.full_config, self.tp_rank, self.tp_size
@@ -183,7 +190,8 @@ class LlamaModel:
         for name, full in (
             ("qkv", qkv_full), ("o", o_full), ("gate_up", gu_full), ("down", down_full)
         ):
-            q, s = ops.fp8_quantize_weight(full)
+            mx = self.weight_dtype == "mxfp4"
+            q, s = (ops.mxfp4_quantize_weight if mx else ops.fp8_quantize_weight)(full)
             if tps > 1:
                 if name == "qkv":
                     q = shard_qkv(q, tpr, tps, fc.q_size, fc.kv_size)
@@ -193,7 +201,9 @@ class LlamaModel:
                     s = shard_gate_up(s, tpr, tps, fc.intermediate_size)
                 else:  # row-parallel: every rank keeps all output channels
                     q = shard_row(q, tpr, tps)
-            self._store_w8(layer, name, q, s)
+                    if mx:  # K-shards are multiples of 64: whole blocks
+                        s = shard_row(s, tpr, tps)
+            (self._store_w4 if mx else self._store_w8)(layer, name, q, s)
         return layer
 
     @staticmethod
@@ -206,6 +216,17 @@ class LlamaModel:
         layer[name + "_q8"] = ops.swizzle_weight_frag_fp8(q)
         layer[name + "_s8"] = s.contiguous()
 
+    @staticmethod
+    def _store_w4(layer, name: str, packed: torch.Tensor, s: torch.Tensor) -> None:
+        if packed.shape[0] % 64 or (packed.shape[1] * 2) % 64:
+            raise ValueError(
+                f"mxfp4 weights need projection shapes in multiples of 64; "
+                f"{name} is {(packed.shape[0], packed.shape[1] * 2)}"
+            )
+        layer[name + "_q4"], layer[name + "_s4"] = ops.swizzle_weight_frag_mxfp4(
+            packed, s
+        )
+
     def _reserve_w8_buffer(self) -> None:
         """The M > 256 route dequantises into one per-device bf16 buffer:
         size it for the largest projection now, so captured graphs never
@@ -215,10 +236,11 @@ class LlamaModel:
         # hand the quantiser's temporaries (full bf16 matrices, fp32 copies)
         # back to the device first: the KV pool is sized from free memory
         torch.cuda.empty_cache()
+        key, per_byte = ("_q4", 2) if self.weight_dtype == "mxfp4" else ("_q8", 1)
         ops.w8_reserve_dequant(
             self.device,
             max(
-                layer[name + "_q8"].numel()
+                layer[name + key].numel() * per_byte
                 for layer in self.layers
                 for name in ("qkv", "o", "gate_up", "down")
             ),
@@ -227,36 +249,45 @@ class LlamaModel:
     @torch.inference_mode()
     def quantize_weights_(self, mode: str = "fp8", simulate: bool = False) -> "LlamaModel":
         """Quantise the qkv/o/gate_up/down projections of a bf16 model in
-        place. simulate=False leaves the model as weight_dtype="fp8" builds
-        it (fp8 twin + scale only). simulate=True is fake-quant: every
+        place; mode is "fp8" or "mxfp4". simulate=False leaves the model as
+        weight_dtype=mode builds it (twin + scales only). simulate=True is
+        fake-quant: every
         projection becomes its dequantised value in the model dtype and the
         bf16 twins are rebuilt — the same maths on the existing kernels, as
         an oracle and an accuracy A/B."""
-        if mode != "fp8":
+        if mode not in ("fp8", "mxfp4"):
             raise ValueError(f"unknown quantisation mode {mode!r}")
-        if self.weight_dtype == "fp8":
-            raise RuntimeError("weights are already fp8")
+        if self.weight_dtype != "auto":
+            raise RuntimeError(f"weights are already {self.weight_dtype}")
         if self.tp_size > 1:
             # row shards would get per-shard scales: not the TP=1 model
             raise RuntimeError(
                 "quantize_weights_ works on an unsharded model; under tensor "
-                "parallelism construct with weight_dtype='fp8'"
+                f"parallelism construct with weight_dtype={mode!r}"
             )
         names = ("qkv", "o", "gate_up", "down")
+        if mode == "mxfp4":
+            quantize, dequantize, store = (
+                ops.mxfp4_quantize_weight, ops.mxfp4_dequantize_weight, self._store_w4
+            )
+        else:
+            quantize, dequantize, store = (
+                ops.fp8_quantize_weight, ops.fp8_dequantize_weight, self._store_w8
+            )
         for layer in self.layers:
             for key in [k for k in layer if k.endswith(("_swz", "_int"))]:
                 del layer[key]
             for name in names:
-                q, s = ops.fp8_quantize_weight(layer[name])
+                q, s = quantize(layer[name])
                 if simulate:
-                    layer[name] = ops.fp8_dequantize_weight(q, s, self.dtype)
+                    layer[name] = dequantize(q, s, self.dtype)
                 else:
                     del layer[name]
-                    self._store_w8(layer, name, q, s)
+                    store(layer, name, q, s)
         if simulate:
             self._build_twins()
         else:
-            self.weight_dtype = "fp8"
+            self.weight_dtype = mode
             self._reserve_w8_buffer()
         return self
 
@@ -327,6 +358,8 @@ class LlamaModel:
     def _linear(self, x: torch.Tensor, layer, name: str) -> torch.Tensor:
         if self.weight_dtype == "fp8":
             return ops.linear_w8(x, layer[name + "_q8"], layer[name + "_s8"])
+        if self.weight_dtype == "mxfp4":
+            return ops.linear_w4(x, layer[name + "_q4"], layer[name + "_s4"])
         return ops.linear(x, layer[name], layer.get(name + "_swz"))
 
     def _row_parallel(self, x: torch.Tensor, layer, name: str) -> torch.Tensor:
@@ -361,6 +394,11 @@ class LlamaModel:
             if self.weight_dtype == "fp8":
                 return ops.linear_w8_rmsnorm_residual(
                     x, layer[name + "_q8"], layer[name + "_s8"], residual,
+                    norm_w, eps,
+                )
+            if self.weight_dtype == "mxfp4":
+                return ops.linear_w4_rmsnorm_residual(
+                    x, layer[name + "_q4"], layer[name + "_s4"], residual,
                     norm_w, eps,
                 )
             return ops.linear_rmsnorm_residual(
@@ -448,7 +486,7 @@ class LlamaModel:
                 self.layers[i + 1]["input_norm"] if i + 1 < n_layers
                 else self.final_norm
             )
-            if self.weight_dtype == "fp8":
+            if self.weight_dtype != "auto":
                 act = ops.swiglu(self._linear(x, layer, "gate_up"))
             else:
                 act = ops.swiglu_linear(

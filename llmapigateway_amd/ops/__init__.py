@@ -48,6 +48,12 @@ from .reference import (  # re-export (fp8 weight quantisation scheme)
     swizzle_weight_frag_fp8,
     unswizzle_weight_frag_fp8,
 )
+from .reference import (  # re-export (MXFP4 weight quantisation scheme)
+    mxfp4_dequantize_weight,
+    mxfp4_quantize_weight,
+    swizzle_weight_frag_mxfp4,
+    unswizzle_weight_frag_mxfp4,
+)
 
 _C = None
 _C_ERR: Optional[str] = None
@@ -243,7 +249,7 @@ class _Scratch:
 _decode_acc = _Scratch(torch.float32)  # flash-decode partial accumulators
 _decode_ml = _Scratch(torch.float32)   # ... and their (max, sum) pairs
 _slabs = _Scratch(torch.float32)       # split-K fp32 slabs of the decode GEMMs
-_w8_dq = _Scratch(torch.bfloat16)      # bf16 image of an fp8 weight (M > 256)
+_w8_dq = _Scratch(torch.bfloat16)      # bf16 image of an fp8 / MXFP4 weight (M > 256)
 
 
 def attention_decode(
@@ -319,6 +325,10 @@ def _skinny_nsk(N: int, K: int) -> int:
 
 
 def _w8_nsk(N: int, K: int) -> int:
+    return _stream_nsk(N, K, 64)
+
+
+def _w4_nsk(N: int, K: int) -> int:
     return _stream_nsk(N, K, 64)
 
 
@@ -671,7 +681,7 @@ def dequant_w8(
 def _w8_gpu_check(x: torch.Tensor) -> None:
     if x.dim() != 2 or x.dtype != torch.bfloat16 or not x.is_contiguous():
         raise RuntimeError(
-            "linear_w8 on GPU needs a contiguous 2-D bf16 activation "
+            "linear_w8 / linear_w4 on GPU need a contiguous 2-D bf16 activation "
             f"(got dim={x.dim()}, dtype={x.dtype}, contiguous={x.is_contiguous()})"
         )
 
@@ -882,6 +892,85 @@ def linear_w8_rmsnorm_residual(
     return rmsnorm_residual(linear_w8(x, q_frag, scale, nsk), residual, norm_w, eps)
 
 
+# ---- MXFP4 weights: W4A16 decode GEMM (csrc/gemm_w4.hip) ----
+
+def dequant_w4(
+    q_frag: torch.Tensor, s_frag: torch.Tensor, out: Optional[torch.Tensor] = None
+) -> torch.Tensor:
+    """Fragment-major MXFP4 twin -> row-major bf16 [N, K]; into `out` when
+    given, else into the per-device buffer dequant_w8 uses (valid until the
+    next call of either)."""
+    K, N = q_frag.shape[0] * 64, q_frag.shape[1] * 16
+    if not q_frag.is_cuda:
+        w = reference.mxfp4_dequantize_weight(
+            *reference.unswizzle_weight_frag_mxfp4(q_frag, s_frag), torch.bfloat16
+        )
+        if out is not None:
+            out.copy_(w)
+            return out
+        return w
+    if out is None:
+        out = w8_reserve_dequant(q_frag.device, N * K)[: N * K].view(N, K)
+    _native().dequant_w4(out, q_frag, s_frag)
+    return out
+
+
+def linear_w4(
+    x: torch.Tensor, q_frag: torch.Tensor, s_frag: torch.Tensor,
+    nsk: Optional[int] = None,
+) -> torch.Tensor:
+    """y = x @ dequant(q, s).T with (q_frag, s_frag) the fragment-major
+    MXFP4 twin (swizzle_weight_frag_mxfp4): e2m1 nibbles and one e8m0 scale
+    per 32 k of a row. GPU: M <= 256 runs the W4A16 streaming kernel
+    (csrc/gemm_w4.hip), larger M dequantises into the per-device bf16 buffer
+    and calls the library GEMM. CPU: the reference."""
+    if not x.is_cuda:
+        return reference.linear_w4(
+            x, *reference.unswizzle_weight_frag_mxfp4(q_frag, s_frag)
+        )
+    _w8_gpu_check(x)
+    M, K = x.shape
+    N = q_frag.shape[1] * 16
+    if M > _W8_MAX_M:
+        return torch.nn.functional.linear(x, dequant_w4(q_frag, s_frag))
+    if nsk is None:
+        nsk = _w4_nsk(N, K)
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    ws = _slabs.get(x.device, nsk * M * N) if nsk > 1 else None
+    _native().gemm_w4(y, x, q_frag, s_frag, ws, nsk)
+    return y
+
+
+def linear_w4_rmsnorm_residual(
+    x: torch.Tensor, q_frag: torch.Tensor, s_frag: torch.Tensor,
+    residual: torch.Tensor, norm_w: torch.Tensor, eps: float = 1e-5,
+    nsk: Optional[int] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(normed, residual) = rmsnorm_residual(linear_w4(x, q_frag, s_frag),
+    residual, norm_w, eps). On the split-K kernel route (nsk > 1) with a
+    covered row width the residual add and the norm run inside the slab
+    reduction; bit-identical to the unfused pair, which every other case
+    runs (LLMAPI_NO_DECODE_FUSION=1 forces it)."""
+    if x.is_cuda and not os.environ.get("LLMAPI_NO_DECODE_FUSION"):
+        _w8_gpu_check(x)
+        M, K = x.shape
+        N = q_frag.shape[1] * 16
+        k = _w4_nsk(N, K) if nsk is None else nsk
+        if (
+            M <= _W8_MAX_M
+            and k > 1
+            and _reduce_norm_covers(N)
+            and residual.is_contiguous()
+        ):
+            return _splitk_norm(
+                lambda y, ws, *tail: _native().gemm_w4(
+                    y, x, q_frag, s_frag, ws, k, *tail
+                ),
+                x, N, k, residual, norm_w, eps,
+            )
+    return rmsnorm_residual(linear_w4(x, q_frag, s_frag, nsk), residual, norm_w, eps)
+
+
 def topk_topp_filter(
     logits: torch.Tensor, topp: torch.Tensor, topk: torch.Tensor
 ) -> torch.Tensor:
@@ -932,6 +1021,13 @@ __all__ = [
     "gemm_w8_m256_rmsnorm_residual",
     "dequant_w8",
     "w8_reserve_dequant",
+    "mxfp4_quantize_weight",
+    "mxfp4_dequantize_weight",
+    "swizzle_weight_frag_mxfp4",
+    "unswizzle_weight_frag_mxfp4",
+    "linear_w4",
+    "linear_w4_rmsnorm_residual",
+    "dequant_w4",
     "attention_prefill",
     "attention_decode",
     "sample",

@@ -465,6 +465,62 @@ void dequant_w8(torch::Tensor out, torch::Tensor q_frag, torch::Tensor scale) {
                                 current_stream()));
 }
 
+// fragment-major MXFP4 weight twin: nibbles [K/64, N/16, 64, 8] (two e2m1
+// per byte) and e8m0 block scales [K/64, N/64, 16, 8], both uint8; returns N
+int check_w4(const torch::Tensor& q_frag, const torch::Tensor& s_frag, int K) {
+    TORCH_CHECK(q_frag.is_cuda() && s_frag.is_cuda(), "q_frag/s_frag must be on GPU");
+    TORCH_CHECK(q_frag.scalar_type() == torch::kUInt8,
+                "q_frag must be uint8 (packed e2m1 nibbles)");
+    TORCH_CHECK(s_frag.scalar_type() == torch::kUInt8,
+                "s_frag must be uint8 (e8m0 block scales)");
+    TORCH_CHECK(q_frag.is_contiguous() && s_frag.is_contiguous());
+    TORCH_CHECK(K > 0 && K % 64 == 0, "K must be a positive multiple of 64");
+    TORCH_CHECK(q_frag.dim() == 4 && q_frag.size(0) == K / 64 &&
+                q_frag.size(2) == 64 && q_frag.size(3) == 8,
+                "q_frag must be the fragment-major [K/64, N/16, 64, 8] twin");
+    const int N = q_frag.size(1) * 16;
+    TORCH_CHECK(N > 0 && N % 64 == 0, "N must be a positive multiple of 64");
+    TORCH_CHECK(s_frag.dim() == 4 && s_frag.size(0) == K / 64 &&
+                s_frag.size(1) == N / 64 && s_frag.size(2) == 16 &&
+                s_frag.size(3) == 8,
+                "s_frag must hold one scale per 32 k of every row "
+                "([K/64, N/64, 16, 8])");
+    return N;
+}
+
+void gemm_w4(torch::Tensor y, torch::Tensor x, torch::Tensor q_frag,
+             torch::Tensor s_frag, c10::optional<torch::Tensor> workspace,
+             int64_t nsk, c10::optional<torch::Tensor> residual,
+             c10::optional<torch::Tensor> norm_weight, double eps,
+             c10::optional<torch::Tensor> out) {
+    check_bf16(x, "x");
+    check_bf16(y, "y");
+    TORCH_CHECK(x.is_contiguous() && y.is_contiguous());
+    TORCH_CHECK(x.dim() == 2 && y.dim() == 2);
+    const int M = x.size(0), K = x.size(1);
+    TORCH_CHECK(M >= 1 && M <= 256, "gemm_w4 covers 1 <= M <= 256");
+    const int N = check_w4(q_frag, s_frag, K);
+    TORCH_CHECK(y.size(0) == M && y.size(1) == N);
+    TORCH_CHECK(nsk >= 1 && nsk <= K / 64, "nsk must be in [1, K/64]");
+    float* ws = workspace_ptr(workspace, nsk * (int64_t)M * N);
+    TORCH_CHECK(nsk == 1 || ws != nullptr, "split-K needs a workspace");
+    const NormTail t = norm_tail(residual, norm_weight, out, M, N, nsk, ws);
+    CHECK_HIP(launch_gemm_w4(y.data_ptr(), ws, x.data_ptr(), q_frag.data_ptr(),
+                             s_frag.data_ptr(), M, N, K, (int)nsk, t.residual,
+                             t.norm_weight, (float)eps, t.out,
+                             current_stream()));
+}
+
+void dequant_w4(torch::Tensor out, torch::Tensor q_frag, torch::Tensor s_frag) {
+    check_bf16(out, "out");
+    TORCH_CHECK(out.is_contiguous() && out.dim() == 2);
+    const int K = out.size(1);
+    const int N = check_w4(q_frag, s_frag, K);
+    TORCH_CHECK(out.size(0) == N, "out must be [N, K]");
+    CHECK_HIP(launch_dequant_w4(out.data_ptr(), q_frag.data_ptr(),
+                                s_frag.data_ptr(), N, K, current_stream()));
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -518,6 +574,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("out") = pybind11::none());
     m.def("dequant_w8", &dequant_w8,
           "fragment-major fp8 twin + scale -> row-major bf16 [N, K]");
+    m.def("gemm_w4", &gemm_w4,
+          "W4A16 skinny decode GEMM y = x @ dequant(q, s).T (1 <= M <= 256), "
+          "q/s the fragment-major MXFP4 twin (e2m1 nibbles, e8m0 block-32 "
+          "scales); residual/norm_weight/out as for gemm_w8",
+          pybind11::arg("y"), pybind11::arg("x"), pybind11::arg("q_frag"),
+          pybind11::arg("s_frag"), pybind11::arg("workspace"),
+          pybind11::arg("nsk"),
+          pybind11::arg("residual") = pybind11::none(),
+          pybind11::arg("norm_weight") = pybind11::none(),
+          pybind11::arg("eps") = 1e-5,
+          pybind11::arg("out") = pybind11::none());
+    m.def("dequant_w4", &dequant_w4,
+          "fragment-major MXFP4 twin -> row-major bf16 [N, K]");
 
     pybind11::class_<BlockAllocator>(m, "BlockAllocator")
         .def(pybind11::init<int64_t>())

@@ -39,6 +39,14 @@ hipError_t launch_gemm_w8(void* y, float* workspace, const void* x,
                           hipStream_t stream);
 hipError_t launch_dequant_w8(void* out, const void* q, const float* scale,
                              int N, int K, hipStream_t stream);
+// gemm_w4.hip
+hipError_t launch_gemm_w4(void* y, float* workspace, const void* x,
+                          const void* q, const void* scale, int M, int N,
+                          int K, int nsk, void* residual,
+                          const void* norm_weight, float eps, void* out,
+                          hipStream_t stream);
+hipError_t launch_dequant_w4(void* out, const void* q, const void* scale,
+                             int N, int K, hipStream_t stream);
 // gemm_w8_m256.hip
 hipError_t launch_gemm_w8_m256(void* y, float* workspace, const void* x,
                                const void* q, const float* scale, int M, int N,

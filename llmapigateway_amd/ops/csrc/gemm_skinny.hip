@@ -25,8 +25,8 @@ struct BBf16 {
     struct Regs { bf16x8 v[GS_NF]; };
     const bf16* p[KMAJOR ? 1 : GS_NF];
     size_t step;  // elements per k-step
-    __device__ __forceinline__ void init(const void* w, int N, int K, int n0,
-                                         int k0, int lane) {
+    __device__ __forceinline__ void init(const void* w, const void*, int N, int K,
+                                         int n0, int k0, int lane) {
         const int lrow = lane & 15, lk = lane >> 4;
         if (KMAJOR) {
             step = (size_t)32 * N;

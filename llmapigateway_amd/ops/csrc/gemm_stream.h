@@ -1,7 +1,8 @@
 // The skinny-M weight-streaming GEMM pipeline for gfx950, written once:
 //   Y[M,N] = X[M,K] · W[N,K]^T, X bf16, fp32 accumulation, M <= 256.
-// gemm_skinny.hip (bf16 weights, row-major or k-major) and gemm_w8.hip (fp8
-// e4m3 weights) instantiate it with a B-operand policy each.
+// gemm_skinny.hip (bf16 weights, row-major or k-major), gemm_w8.hip (fp8
+// e4m3 weights) and gemm_w4.hip (MXFP4 weights) instantiate it with a
+// B-operand policy each.
 //
 // - grid = (N/64 n-stripes) x (split-K slices). One workgroup owns ALL M
 //   rows of a 64-wide N stripe for its K-slice, so W is streamed exactly
@@ -21,12 +22,15 @@
 //   KSTEP                  k-depth of one pipeline step (KSTEP/32 MFMAs per
 //                          accumulator, issued in increasing k)
 //   Regs                   one step's B registers for the stripe
-//   init(w, N, K, n0, k0, lane)   point at the slice's first step
+//   init(w, aux, N, K, n0, k0, lane)   point at the slice's first step
 //   load(regs, S)          issue the loads of step S (relative)
 //   bump(steps)            advance
 //   frag(regs, n, h)       MFMA B fragment of n-fragment n, k32 half h
 //   SCALED                 multiply the accumulator by scale[col] before
 //                          the store
+// aux is the launch's second weight operand: the fp32 channel scales of a
+// SCALED policy, or whatever else a policy streams beside w (gemm_w4.hip:
+// the e8m0 block scales); a policy that needs none ignores it.
 #pragma once
 
 #include "common.h"
@@ -69,7 +73,7 @@ __global__ void gemm_stream_kernel(
     float* __restrict__ yw,          // [nsk, M, N] fp32 slabs (SPLITK)
     const bf16* __restrict__ x,      // [M, K]
     const void* __restrict__ w,      // the policy's weight layout
-    const float* __restrict__ scale, // [N] (B::SCALED)
+    const void* __restrict__ aux,    // [N] fp32 scales (B::SCALED) / policy's own
     int M,
     int N,
     int K,
@@ -101,7 +105,7 @@ __global__ void gemm_stream_kernel(
         ap[f] = x + (size_t)(r < M ? r : 0) * K + k0 + lk * 8;
     }
     B bp;
-    bp.init(w, N, K, n0, k0, lane);
+    bp.init(w, aux, N, K, n0, k0, lane);
 
     const int nsteps = (k1 - k0) / KS;  // K and kslice are KS-aligned
     if (nsteps > 0 && m_base < M) {
@@ -190,7 +194,7 @@ __global__ void gemm_stream_kernel(
     float sc[GS_NF];
 #pragma unroll
     for (int n = 0; n < GS_NF; ++n)
-        sc[n] = B::SCALED ? scale[n0 + n * 16 + lrow] : 1.f;
+        sc[n] = B::SCALED ? ((const float*)aux)[n0 + n * 16 + lrow] : 1.f;
     float* slab = yw + (size_t)(SPLITK ? blockIdx.y : 0) * M * N;
 #pragma unroll
     for (int f = 0; f < MF; ++f)
@@ -212,14 +216,14 @@ __global__ void gemm_stream_kernel(
 template <class B>
 static hipError_t launch_gemm_stream(
     void* y, float* workspace, const void* x, const void* w,
-    const float* scale, int M, int N, int K, int nsk, hipStream_t stream) {
+    const void* aux, int M, int N, int K, int nsk, hipStream_t stream) {
     // prefer more waves over more rows per wave: MF=1 up to 8 waves (M <= 128)
     const int mf = M > 128 ? 2 : 1;
     dim3 grid(N / GS_NT, nsk);
     dim3 block(ceil_div_i(M, 16 * mf) * WAVE_SIZE);
 #define GS_LAUNCH(MFV, SPLIT)                                                  \
     gemm_stream_kernel<B, MFV, SPLIT><<<grid, block, 0, stream>>>(             \
-        (bf16*)y, workspace, (const bf16*)x, w, scale, M, N, K, nsk)
+        (bf16*)y, workspace, (const bf16*)x, w, aux, M, N, K, nsk)
     if (nsk == 1) {
         if (mf == 1) GS_LAUNCH(1, false);
         else GS_LAUNCH(2, false);

@@ -32,8 +32,8 @@ struct BFp8Frag {
     size_t step;
     // the stripe's four fragment rows are adjacent: 1 KiB apart; one k64
     // step further is a whole [N/16, 64, 16] plane = 64*N bytes
-    __device__ __forceinline__ void init(const void* q, int N, int K, int n0,
-                                         int k0, int lane) {
+    __device__ __forceinline__ void init(const void* q, const void*, int N, int K,
+                                         int n0, int k0, int lane) {
         step = (size_t)64 * N;
         p = (const uint8_t*)q + (size_t)(k0 / 64) * step +
             ((size_t)(n0 / 16) * 64 + lane) * 16;

@@ -165,6 +165,120 @@ def linear_w8(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor) -> torch.Te
     return (x.float() @ w.T).to(x.dtype)
 
 
+# OCP MXFP4: e2m1 elements (sign, 2 exponent bits, 1 mantissa bit), one e8m0
+# power-of-two scale per block of 32 consecutive k. The 16 element codes:
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+_E2M1_TABLE = torch.tensor(_E2M1 + tuple(-v for v in _E2M1), dtype=torch.float32)
+MXFP4_BLOCK = 32
+
+
+def mxfp4_quantize_weight(w: torch.Tensor):
+    """Weight quantisation to MXFP4: w [N, K] -> (packed uint8 [N, K/2],
+    scale uint8 [N, K/32]).
+
+    A block is 32 consecutive k of one row. Its scale is the smallest power
+    of two s with amax/s <= 6, so nothing clips (the rule of
+    fp8_quantize_weight), stored as e8m0: byte = exponent + 127 with the
+    exponent clamped to [-126, 127] (bytes 0 and 255 never appear); an
+    all-zero block gets byte 127. Elements round to nearest-even onto the
+    e2m1 grid {0, .5, 1, 1.5, 2, 3, 4, 6} x sign; even k sits in the low
+    nibble of a byte, odd k in the high nibble."""
+    N, K = w.shape
+    assert K % MXFP4_BLOCK == 0
+    b = w.float().view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = b.abs().amax(dim=-1)
+    # amax = m * 2^e with m in [0.5, 1), and 6 * 2^t = 0.75 * 2^(t+3): the
+    # smallest t with amax <= 6 * 2^t is e-3 when m <= 0.75, else e-2
+    m, e = torch.frexp(amax)
+    t = torch.where(m <= 0.75, e - 3, e - 2).clamp(-126, 127)
+    t = torch.where(amax > 0, t, torch.zeros_like(t))
+    v = b / torch.ldexp(torch.ones_like(amax), t).unsqueeze(-1)
+    # round to nearest, ties to the even code: the grid step is 0.5 below 2,
+    # 1 below 4 and 2 above, and torch.round's even multiple of the step is
+    # the code with a clear mantissa bit. |v| <= 6 by the choice of t (the
+    # exponent clamp can only raise t).
+    a = v.abs()
+    step = torch.where(a < 2, 0.5, torch.where(a < 4, 1.0, 2.0))
+    g = torch.round(a / step) * step
+    code = torch.where(g < 2, g * 2, torch.where(g <= 4, g + 2, torch.full_like(g, 7)))
+    code = code.to(torch.uint8) | (((v < 0) & (g > 0)).to(torch.uint8) << 3)
+    code = code.view(N, K)
+    packed = code[:, 0::2] | (code[:, 1::2] << 4)
+    return packed.contiguous(), (t + 127).to(torch.uint8)
+
+
+def mxfp4_dequantize_weight(
+    packed: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype = torch.bfloat16
+) -> torch.Tensor:
+    """packed [N, K/2], scale [N, K/32] -> [N, K]; exact for bf16 (and
+    wider): one mantissa bit, and the scale only shifts the exponent."""
+    N, K = packed.shape[0], packed.shape[1] * 2
+    codes = torch.stack([packed & 15, packed >> 4], dim=-1).view(N, K)
+    vals = _E2M1_TABLE.to(packed.device)[codes.long()]
+    s = torch.ldexp(
+        torch.ones(scale.shape, dtype=torch.float32, device=scale.device),
+        scale.to(torch.int32) - 127,
+    )
+    blocks = vals.view(N, K // MXFP4_BLOCK, MXFP4_BLOCK) * s.unsqueeze(-1)
+    return blocks.view(N, K).to(dtype)
+
+
+def swizzle_weight_frag_mxfp4(packed: torch.Tensor, scale: torch.Tensor):
+    """packed [N, K/2], scale [N, K/32] -> fragment-major (q_frag
+    [K/64, N/16, 64, 8], s_frag [K/64, N/64, 16, 8]) for gemm_w4.
+
+    q_frag[k64][n16][lane][j] = packed[n16*16 + (lane&15)][k64*32 +
+    (j>>2)*16 + (lane>>4)*4 + (j&3)]: the fp8 fragment convention in
+    nibbles — each 512 B row is one wave's mfma_f32_16x16x32_bf16
+    B-fragments for two consecutive k-steps (bytes 0-3 then 4-7), one 8-byte
+    load per lane; the nibble order inside a byte is unchanged.
+    s_frag[k64][n64][r][f*2 + h] = scale[n64*64 + f*16 + r][k64*2 + h]: the
+    8 bytes at [r] are the block scales lane r (and r+16, r+32, r+48) needs
+    for its four n-fragments f and two k32 halves h of that step."""
+    N, K = packed.shape[0], packed.shape[1] * 2
+    assert K % 64 == 0 and N % 64 == 0
+    assert scale.shape == (N, K // MXFP4_BLOCK)
+    # byte = k64*32 + h*16 + g*4 + e, n = n16*16 + r; lane = g*16 + r, j = h*4 + e
+    q_frag = (
+        packed.view(N // 16, 16, K // 64, 2, 4, 4)
+        .permute(2, 0, 4, 1, 3, 5)
+        .reshape(K // 64, N // 16, 64, 8)
+        .contiguous()
+    )
+    s_frag = (
+        scale.view(N // 64, 4, 16, K // 64, 2)
+        .permute(3, 0, 2, 1, 4)
+        .reshape(K // 64, N // 64, 16, 8)
+        .contiguous()
+    )
+    return q_frag, s_frag
+
+
+def unswizzle_weight_frag_mxfp4(q_frag: torch.Tensor, s_frag: torch.Tensor):
+    """Inverse of swizzle_weight_frag_mxfp4: -> (packed [N, K/2], scale
+    [N, K/32])."""
+    k64, n16 = q_frag.shape[0], q_frag.shape[1]
+    packed = (
+        q_frag.view(k64, n16, 4, 16, 2, 4)
+        .permute(1, 3, 0, 4, 2, 5)
+        .reshape(n16 * 16, k64 * 32)
+        .contiguous()
+    )
+    scale = (
+        s_frag.view(k64, n16 // 4, 16, 4, 2)
+        .permute(1, 3, 2, 0, 4)
+        .reshape(n16 * 16, k64 * 2)
+        .contiguous()
+    )
+    return packed, scale
+
+
+def linear_w4(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """y = x @ dequant(packed, scale).T with the row-major MXFP4 pair."""
+    w = mxfp4_dequantize_weight(packed, scale, torch.float32)
+    return (x.float() @ w.T).to(x.dtype)
+
+
 def kv_cache_write(
     k: torch.Tensor,
     v: torch.Tensor,
