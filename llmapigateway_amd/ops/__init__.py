@@ -915,6 +915,131 @@ def dequant_w4(
     return out
 
 
+def _w4_m256_default(M: int, N: int, K: int) -> dict:
+    """nf and nsk of the macro-tile MXFP4 kernel where nothing was measured:
+    the rule of _w8_m256_default (nf by gemm_m256's rule, nsk from
+    _m256_nsk)."""
+    return _w8_m256_default(M, N, K)
+
+
+# (N, K) -> {measured M: (nf, nsk) or None}. Cold-cache sweep over nf in
+# {4,8} x nsk in {1,2,4,8} (tools/gemm_w4_bench.py --sweep,
+# profiles/r08_w4_macro.md); each comment is "macro vs streaming" in us,
+# medians of 3 rounds. A cell is None where no macro configuration's
+# three-round range lay wholly below the MXFP4 streaming kernel's.
+_W4_M256_TABLE = {
+    (6144, 4096): {      # llama-3-8b qkv
+        64: (4, 8),      # 19.1 vs 22.3
+        128: (8, 8),     # 22.8 vs 38.6
+        256: (8, 4),     # 28.4 vs 56.8
+    },
+    (4096, 4096): {      # llama-3-8b o
+        64: None,        # best 16.2 vs 12.8
+        128: (4, 4),     # 19.3 vs 20.3
+        256: (4, 4),     # 22.5 vs 28.9
+    },
+    (28672, 4096): {     # llama-3-8b gate_up
+        64: (4, 2),      # 38.2 vs 49.4
+        128: (4, 1),     # 49.9 vs 94.5
+        256: (8, 1),     # 67.6 vs 152.5
+    },
+    (4096, 14336): {     # llama-3-8b down
+        64: None,        # best 29.9 vs 26.6
+        128: (4, 8),     # 32.2 vs 47.1
+        256: (8, 8),     # 44.4 vs 73.2
+    },
+    (10240, 8192): {     # llama-3-70b qkv
+        64: (8, 8),      # 31.4 vs 51.4
+        128: (4, 4),     # 43.3 vs 98.6
+        256: (4, 4),     # 72.3 vs 156.4
+    },
+    (8192, 8192): {      # llama-3-70b o
+        64: (4, 8),      # 24.9 vs 29.7
+        128: (8, 8),     # 33.0 vs 52.2
+        256: (8, 4),     # 49.0 vs 82.5
+    },
+    (57344, 8192): {     # llama-3-70b gate_up
+        64: (4, 1),      # 111.8 vs 188.5
+        128: (8, 1),     # 151.8 vs 369.5
+        256: (8, 1),     # 251.9 vs 595.1
+    },
+    (8192, 28672): {     # llama-3-70b down
+        64: (4, 8),      # 62.0 vs 95.1
+        128: (8, 8),     # 84.3 vs 171.7
+        256: (8, 4),     # 139.0 vs 269.3
+    },
+}
+_W4_M256_MS = (64, 128, 256)  # the batch sizes the sweep measured
+
+
+def _w4_m256_config(M: int, N: int, K: int) -> Optional[dict]:
+    """Measured dispatch table of the macro-tile MXFP4 kernel
+    (csrc/gemm_w4_m256.hip) against the streaming MXFP4 kernel. Returns
+    {"nf", "nsk"}, or None to keep the streaming kernel. The lookup is
+    _w8_m256_config's: only the measured shapes have entries; a measured M
+    takes its own cell; an M between two measured batch sizes takes the
+    upper one's configuration, and only where the macro kernel won at BOTH
+    ends; below the smallest measured M nothing is assumed."""
+    row = _W4_M256_TABLE.get((N, K))
+    if row is None or not (_W4_M256_MS[0] <= M <= _W4_M256_MS[-1]):
+        return None
+    hi = next(i for i, m in enumerate(_W4_M256_MS) if m >= M)
+    cell = row[_W4_M256_MS[hi]]
+    if cell is None or (M != _W4_M256_MS[hi] and row[_W4_M256_MS[hi - 1]] is None):
+        return None
+    return {"nf": cell[0], "nsk": cell[1]}
+
+
+def _w4_macro_config(M: int, N: int, K: int) -> Optional[dict]:
+    """The macro-tile route of linear_w4 for this call, or None. Opt-in:
+    LLMAPI_W4_MACRO_MIN_M=m (read at call time) sends m <= M <= 256 to
+    gemm_w4_m256 wherever the measured table has an entry."""
+    knob = os.environ.get("LLMAPI_W4_MACRO_MIN_M")
+    if not knob or not (int(knob) <= M <= _W8_MAX_M):
+        return None
+    return _w4_m256_config(M, N, K)
+
+
+def gemm_w4_m256(
+    x: torch.Tensor, q_frag: torch.Tensor, s_frag: torch.Tensor,
+    nf: Optional[int] = None, nsk: Optional[int] = None,
+) -> torch.Tensor:
+    """y = x @ dequant(q, s).T on the macro-tile W4A16 kernel
+    (csrc/gemm_w4_m256.hip): the structure of gemm_w8_m256 with the MXFP4
+    twin converted once per workgroup into the LDS tile. M <= 256; nf in
+    {4, 8} is the column-tile width in 16-col fragments."""
+    M, K = x.shape
+    N = q_frag.shape[1] * 16
+    cfg = _w4_m256_default(M, N, K)
+    if nf is None:
+        nf = cfg["nf"]
+    if nsk is None:
+        nsk = cfg["nsk"] if nf == cfg["nf"] else _m256_nsk(N, K, nf)
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    ws = _slabs.get(x.device, nsk * M * N) if nsk > 1 else None
+    _native().gemm_w4_m256(y, x, q_frag, s_frag, ws, nsk, nf)
+    return y
+
+
+def gemm_w4_m256_rmsnorm_residual(
+    x: torch.Tensor, q_frag: torch.Tensor, s_frag: torch.Tensor,
+    residual: torch.Tensor, norm_w: torch.Tensor, eps: float, nf: int,
+    nsk: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """rmsnorm_residual(gemm_w4_m256(x, q_frag, s_frag), residual, norm_w)
+    with the residual add and the norm fused into the split-K slab
+    reduction; residual is updated in place, bit-identical to the unfused
+    pair. Needs nsk > 1."""
+    if nsk < 2:
+        raise ValueError("fused reduce+norm needs split-K slabs (nsk > 1)")
+    return _splitk_norm(
+        lambda y, ws, *tail: _native().gemm_w4_m256(
+            y, x, q_frag, s_frag, ws, nsk, nf, *tail
+        ),
+        x, q_frag.shape[1] * 16, nsk, residual, norm_w, eps,
+    )
+
+
 def linear_w4(
     x: torch.Tensor, q_frag: torch.Tensor, s_frag: torch.Tensor,
     nsk: Optional[int] = None,
@@ -923,7 +1048,10 @@ def linear_w4(
     MXFP4 twin (swizzle_weight_frag_mxfp4): e2m1 nibbles and one e8m0 scale
     per 32 k of a row. GPU: M <= 256 runs the W4A16 streaming kernel
     (csrc/gemm_w4.hip), larger M dequantises into the per-device bf16 buffer
-    and calls the library GEMM. CPU: the reference."""
+    and calls the library GEMM. With LLMAPI_W4_MACRO_MIN_M=m set and no
+    explicit nsk, m <= M <= 256 runs the macro-tile kernel
+    (csrc/gemm_w4_m256.hip) for the shapes _w4_m256_config lists. CPU: the
+    reference."""
     if not x.is_cuda:
         return reference.linear_w4(
             x, *reference.unswizzle_weight_frag_mxfp4(q_frag, s_frag)
@@ -934,6 +1062,9 @@ def linear_w4(
     if M > _W8_MAX_M:
         return torch.nn.functional.linear(x, dequant_w4(q_frag, s_frag))
     if nsk is None:
+        macro = _w4_macro_config(M, N, K)
+        if macro is not None:
+            return gemm_w4_m256(x, q_frag, s_frag, **macro)
         nsk = _w4_nsk(N, K)
     y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
     ws = _slabs.get(x.device, nsk * M * N) if nsk > 1 else None
@@ -950,11 +1081,26 @@ def linear_w4_rmsnorm_residual(
     residual, norm_w, eps). On the split-K kernel route (nsk > 1) with a
     covered row width the residual add and the norm run inside the slab
     reduction; bit-identical to the unfused pair, which every other case
-    runs (LLMAPI_NO_DECODE_FUSION=1 forces it)."""
+    runs (LLMAPI_NO_DECODE_FUSION=1 forces it). The same holds on the
+    macro-tile route (LLMAPI_W4_MACRO_MIN_M, see linear_w4) with that
+    kernel's nsk."""
     if x.is_cuda and not os.environ.get("LLMAPI_NO_DECODE_FUSION"):
         _w8_gpu_check(x)
         M, K = x.shape
         N = q_frag.shape[1] * 16
+        macro = _w4_macro_config(M, N, K) if nsk is None else None
+        if macro is not None:
+            if (
+                macro["nsk"] > 1
+                and _reduce_norm_covers(N)
+                and residual.is_contiguous()
+            ):
+                return gemm_w4_m256_rmsnorm_residual(
+                    x, q_frag, s_frag, residual, norm_w, eps, **macro
+                )
+            return rmsnorm_residual(
+                gemm_w4_m256(x, q_frag, s_frag, **macro), residual, norm_w, eps
+            )
         k = _w4_nsk(N, K) if nsk is None else nsk
         if (
             M <= _W8_MAX_M
@@ -1027,6 +1173,8 @@ __all__ = [
     "unswizzle_weight_frag_mxfp4",
     "linear_w4",
     "linear_w4_rmsnorm_residual",
+    "gemm_w4_m256",
+    "gemm_w4_m256_rmsnorm_residual",
     "dequant_w4",
     "attention_prefill",
     "attention_decode",

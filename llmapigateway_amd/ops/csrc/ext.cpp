@@ -511,6 +511,34 @@ void gemm_w4(torch::Tensor y, torch::Tensor x, torch::Tensor q_frag,
                              current_stream()));
 }
 
+void gemm_w4_m256(torch::Tensor y, torch::Tensor x, torch::Tensor q_frag,
+                  torch::Tensor s_frag, c10::optional<torch::Tensor> workspace,
+                  int64_t nsk, int64_t nf,
+                  c10::optional<torch::Tensor> residual,
+                  c10::optional<torch::Tensor> norm_weight, double eps,
+                  c10::optional<torch::Tensor> out) {
+    check_bf16(x, "x");
+    check_bf16(y, "y");
+    TORCH_CHECK(x.is_contiguous() && y.is_contiguous());
+    TORCH_CHECK(x.dim() == 2 && y.dim() == 2);
+    const int M = x.size(0), K = x.size(1);
+    TORCH_CHECK(M >= 1 && M <= 256, "gemm_w4_m256 covers 1 <= M <= 256");
+    const int N = check_w4(q_frag, s_frag, K);
+    TORCH_CHECK(y.size(0) == M && y.size(1) == N);
+    TORCH_CHECK(nf == 4 || nf == 8, "nf must be 4 or 8");
+    TORCH_CHECK(N % (16 * nf) == 0, "N must be a multiple of 16*nf");
+    // nsk may exceed K/64: a slice without k-tiles writes zeros
+    TORCH_CHECK(nsk >= 1 && nsk <= 64, "nsk must be in [1, 64]");
+    float* ws = workspace_ptr(workspace, nsk * (int64_t)M * N);
+    TORCH_CHECK(nsk == 1 || ws != nullptr, "split-K needs a workspace");
+    const NormTail t = norm_tail(residual, norm_weight, out, M, N, nsk, ws);
+    CHECK_HIP(launch_gemm_w4_m256(y.data_ptr(), ws, x.data_ptr(),
+                                  q_frag.data_ptr(), s_frag.data_ptr(), M, N,
+                                  K, (int)nsk, (int)nf, t.residual,
+                                  t.norm_weight, (float)eps, t.out,
+                                  current_stream()));
+}
+
 void dequant_w4(torch::Tensor out, torch::Tensor q_frag, torch::Tensor s_frag) {
     check_bf16(out, "out");
     TORCH_CHECK(out.is_contiguous() && out.dim() == 2);
@@ -581,6 +609,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("y"), pybind11::arg("x"), pybind11::arg("q_frag"),
           pybind11::arg("s_frag"), pybind11::arg("workspace"),
           pybind11::arg("nsk"),
+          pybind11::arg("residual") = pybind11::none(),
+          pybind11::arg("norm_weight") = pybind11::none(),
+          pybind11::arg("eps") = 1e-5,
+          pybind11::arg("out") = pybind11::none());
+    m.def("gemm_w4_m256", &gemm_w4_m256,
+          "macro-tile W4A16 decode GEMM y = x @ dequant(q, s).T (1 <= M <= "
+          "256): the MXFP4 twin is converted once per workgroup into the LDS "
+          "tile of the register-staged gemm_m256 structure; "
+          "residual/norm_weight/out as for gemm_w8",
+          pybind11::arg("y"), pybind11::arg("x"), pybind11::arg("q_frag"),
+          pybind11::arg("s_frag"), pybind11::arg("workspace"),
+          pybind11::arg("nsk"), pybind11::arg("nf"),
           pybind11::arg("residual") = pybind11::none(),
           pybind11::arg("norm_weight") = pybind11::none(),
           pybind11::arg("eps") = 1e-5,

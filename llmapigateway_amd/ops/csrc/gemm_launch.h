@@ -53,4 +53,10 @@ hipError_t launch_gemm_w8_m256(void* y, float* workspace, const void* x,
                                int K, int nsk, int nf, void* residual,
                                const void* norm_weight, float eps, void* out,
                                hipStream_t stream);
+// gemm_w4_m256.hip
+hipError_t launch_gemm_w4_m256(void* y, float* workspace, const void* x,
+                               const void* q, const void* scale, int M, int N,
+                               int K, int nsk, int nf, void* residual,
+                               const void* norm_weight, float eps, void* out,
+                               hipStream_t stream);
 }

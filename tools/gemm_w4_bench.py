@@ -1,9 +1,12 @@
-"""Cold-cache timing of the MXFP4 (W4A16) decode GEMM route against the fp8
-(W8A16) streaming route and the bf16 route on the decode projection shapes
-of llama-3-8b and llama-3-70b.
+"""Cold-cache timing of the MXFP4 (W4A16) decode GEMM routes against the fp8
+(W8A16) routes and the bf16 route on the decode projection shapes of
+llama-3-8b and llama-3-70b.
 
-Three routes: bf16 (ops.linear with the twin the bf16 model builds), fp8
-streaming (csrc/gemm_w8.hip) and mxfp4 streaming (csrc/gemm_w4.hip).
+Five routes: bf16 (ops.linear with the twin the bf16 model builds), fp8
+streaming (csrc/gemm_w8.hip), fp8 macro-tile (csrc/gemm_w8_m256.hip, at the
+configuration ops._w8_m256_config lists, else the defaults), mxfp4 streaming
+(csrc/gemm_w4.hip) and mxfp4 macro-tile (csrc/gemm_w4_m256.hip, at the
+configuration ops._w4_m256_config lists, else the defaults).
 
 Each route cycles through enough weight copies (>= 1.5 GB) that no copy is
 still in the 256 MB L3 when its turn comes again, as in the engine, where a
@@ -16,6 +19,12 @@ with the bytes each route has to stream and the rate that implies. Run on
 the GPU box:
 
     python tools/gemm_w4_bench.py [--ms=1,16,64] [M N K]
+    python tools/gemm_w4_bench.py --sweep [--ms=96,192] [M N K]
+
+--sweep times nf in {4,8} x nsk in {1,2,4,8} of the mxfp4 macro route beside
+the other four routes, in the same alternation, at M in {16,64,128,256} on
+every shape (or the one given); ops._W4_M256_TABLE is filled from its
+output.
 """
 
 import os
@@ -39,7 +48,9 @@ SHAPES = [
     ("70b down", 8192, 28672),
 ]
 MS = (1, 16, 64)
+SWEEP_MS = (16, 64, 128, 256)
 ROTATE_BYTES = 1536 << 20
+SWEEP = [(nf, nsk) for nf in (4, 8) for nsk in (1, 2, 4, 8)]
 
 
 def timed(fn, iters):
@@ -69,22 +80,42 @@ def fmt(t):
     return f"{t[0]:.1f} ({t[1]:.1f}-{t[2]:.1f})"
 
 
+def table_or_default(config, default, M, N, K):
+    """(kwargs, tag) of a macro route: its table entry, else its defaults."""
+    cfg = config(M, N, K)
+    if cfg is not None:
+        return cfg, "table"
+    return default(M, N, K), "default"
+
+
 def main():
     assert torch.cuda.is_available() and ops.have_native()
     dev = "cuda:0"
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    sweep = "--sweep" in sys.argv
     shapes = SHAPES
     if len(args) == 3:
         shapes = [("custom",) + tuple(int(a) for a in args[1:3])]
-    ms = MS if len(args) != 3 else (int(args[0]),)
+    ms = (SWEEP_MS if sweep else MS) if len(args) != 3 else (int(args[0]),)
     for a in sys.argv[1:]:
         if a.startswith("--ms="):
             ms = tuple(int(m) for m in a[5:].split(","))
-    print(
-        "shape, M, bf16 us, fp8 us, mxfp4 us, mxfp4/fp8 speedup, "
-        "mxfp4/bf16 speedup, bf16 GB/s, fp8 GB/s, mxfp4 GB/s, max err fp8, "
-        "max err mxfp4"
-    )
+    if sweep:
+        print(
+            "shape, M, bf16 us, fp8 stream us, fp8 macro us, fp8 macro cfg, "
+            "mxfp4 stream us, "
+            + ", ".join(f"nf{nf}/nsk{nsk} us" for nf, nsk in SWEEP)
+            + ", max err"
+        )
+    else:
+        print(
+            "shape, M, bf16 us, fp8 stream us, fp8 macro us, fp8 macro cfg, "
+            "mxfp4 stream us, mxfp4 macro us, mxfp4 macro cfg, "
+            "mxfp4 macro/stream speedup, mxfp4 macro/bf16 speedup, "
+            "mxfp4 stream/fp8 stream speedup, bf16 GB/s, fp8 stream GB/s, "
+            "mxfp4 stream GB/s, mxfp4 macro GB/s, max err fp8, "
+            "max err mxfp4 stream, max err mxfp4 macro"
+        )
     for name, N, K in shapes:
         n16 = max(2, -(-ROTATE_BYTES // (N * K * 2)))
         n8 = max(2, -(-ROTATE_BYTES // (N * K)))
@@ -128,18 +159,50 @@ def main():
             def f4(i):
                 return ops.linear_w4(x, q4[i % n4], s4[i % n4])
 
-            a, b, c = rounds(
-                [f16, f8, f4], [2 * n16 + 20, 2 * n8 + 20, 2 * n4 + 20]
+            def m8(nf, nsk):
+                return lambda i: ops.gemm_w8_m256(
+                    x, q8[i % n8], s8[i % n8], nf=nf, nsk=nsk
+                )
+
+            def m4(nf, nsk):
+                return lambda i: ops.gemm_w4_m256(
+                    x, q4[i % n4], s4[i % n4], nf=nf, nsk=nsk
+                )
+
+            it16, it8, it4 = 2 * n16 + 20, 2 * n8 + 20, 2 * n4 + 20
+            c8, tag8 = table_or_default(ops._w8_m256_config, ops._w8_m256_default, M, N, K)
+            fm8 = m8(c8["nf"], c8["nsk"])
+            if sweep:
+                cfgs = [c for c in SWEEP if N % (16 * c[0]) == 0]
+                err = max(err_of(m4(*c)(0), deq4) for c in cfgs)
+                ts = rounds(
+                    [f16, f8, fm8, f4] + [m4(*c) for c in cfgs],
+                    [it16, it8, it8, it4] + [it4] * len(cfgs),
+                )
+                cells = [fmt(t) for t in ts]
+                cells.insert(3, f"nf{c8['nf']}/nsk{c8['nsk']} {tag8}")
+                print(
+                    f"{name} ({N}x{K}), {M}, " + ", ".join(cells) + f", {err:.4f}",
+                    flush=True,
+                )
+                continue
+            c4, tag4 = table_or_default(ops._w4_m256_config, ops._w4_m256_default, M, N, K)
+            fm4 = m4(c4["nf"], c4["nsk"])
+            a, b, bm, c, cm = rounds(
+                [f16, f8, fm8, f4, fm4], [it16, it8, it8, it4, it4]
             )
             act = M * (K + N) * 2
             by16 = N * K * 2 + act
             by8 = N * K + N * 4 + act
             by4 = N * K * 17 // 32 + act
             print(
-                f"{name} ({N}x{K}), {M}, {fmt(a)}, {fmt(b)}, {fmt(c)}, "
-                f"{b[0] / c[0]:.2f}, {a[0] / c[0]:.2f}, {by16 / a[0] / 1e3:.0f}, "
+                f"{name} ({N}x{K}), {M}, {fmt(a)}, {fmt(b)}, {fmt(bm)}, "
+                f"nf{c8['nf']}/nsk{c8['nsk']} {tag8}, {fmt(c)}, {fmt(cm)}, "
+                f"nf{c4['nf']}/nsk{c4['nsk']} {tag4}, {c[0] / cm[0]:.2f}, "
+                f"{a[0] / cm[0]:.2f}, {b[0] / c[0]:.2f}, {by16 / a[0] / 1e3:.0f}, "
                 f"{by8 / b[0] / 1e3:.0f}, {by4 / c[0] / 1e3:.0f}, "
-                f"{err_of(f8(0), deq8):.4f}, {err_of(f4(0), deq4):.4f}",
+                f"{by4 / cm[0] / 1e3:.0f}, {err_of(f8(0), deq8):.4f}, "
+                f"{err_of(f4(0), deq4):.4f}, {err_of(fm4(0), deq4):.4f}",
                 flush=True,
             )
         del w16, tw, q8, s8, q4, s4, deq8, deq4, w0
@@ -148,3 +211,4 @@ def main():
 
 if __name__ == "__main__":
     main()
+
