@@ -50,6 +50,7 @@ class EngineSpec(BaseModel):
     kv_block_size: Optional[int] = None
     kv_dtype: str = "auto"               # "auto" (= compute dtype) | "fp8"
     weight_dtype: str = "auto"           # "auto" (= compute dtype) | "fp8" (e4m3 projections) | "mxfp4" (e2m1, block-32 scales)
+    sliding_window: Optional[int] = None  # attention window; None = the preset's, 0 = off
     fail_rate: float = 0.0               # failure injection: P(request fails)
     fail_requests: Optional[int] = None  # failure injection: fail first N requests
 
@@ -74,7 +75,8 @@ class ProviderDetails(BaseModel):
             if u.netloc:
                 updates["model"] = u.netloc
             q = parse_qs(u.query)
-            for key in ("device", "tp", "max_batch_size", "kv_block_size", "fail_requests"):
+            for key in ("device", "tp", "max_batch_size", "kv_block_size", "fail_requests",
+                        "sliding_window"):
                 if key in q:
                     updates[key] = int(q[key][0])
             if "dtype" in q:

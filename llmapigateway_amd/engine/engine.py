@@ -20,6 +20,7 @@ re-admission re-prefills prompt+generated, re-hitting the prefix cache).
 
 from __future__ import annotations
 
+import dataclasses
 import itertools
 import logging
 import os
@@ -168,11 +169,24 @@ class LLMEngine:
         prefill_budget: int = 4096,
         kv_dtype: str = "auto",
         weight_dtype: str = "auto",
+        sliding_window: Optional[int] = None,
         tokenizer: Optional[object] = None,
         admit_min_batch: Optional[int] = None,
         admit_max_wait: Optional[float] = None,
     ):
         full_config = get_model_config(model) if isinstance(model, str) else model
+        if sliding_window is not None:
+            # overrides the preset's window; 0 turns it off
+            if sliding_window < 0:
+                raise ValueError(f"sliding_window must be >= 0, got {sliding_window}")
+            full_config = dataclasses.replace(
+                full_config, sliding_window=int(sliding_window) or None
+            )
+        # attention window of the model (0 = none): a constant of the engine
+        self.sliding_window = int(full_config.sliding_window or 0)
+        # windowed models give KV blocks back as they fall out of the
+        # window; tests switch this off to compare with blocks kept
+        self._swa_release = True
         self.full_config = full_config
         config = full_config.scaled_for_tp(tp_size) if tp_size > 1 else full_config
         self.config = config
@@ -408,6 +422,20 @@ class LLMEngine:
             admitted.append(req)
         return admitted
 
+    def _release_window(self, req: EngineRequest, next_pos: int) -> None:
+        """Sliding window: the next query of `req` sits at position
+        `next_pos`, so no key below next_pos - W + 1 is read again. Give
+        those blocks back (caller holds the lock); the forwards that read
+        them are already issued, and whoever gets the blocks next writes
+        them in a later forward of the same stream."""
+        if not (self.sliding_window and self._swa_release) or req.bt_slot is None:
+            return
+        n = self.kv.manager.release_before(
+            req.block_table, next_pos - self.sliding_window + 1
+        )
+        if n:
+            self._bt_np[req.bt_slot, : len(req.block_table)] = req.block_table
+
     def _free_slot(self, req: EngineRequest) -> None:
         if req.bt_slot is not None:
             self._slot_pool.append(req.bt_slot)
@@ -532,6 +560,7 @@ class LLMEngine:
                                 req.block_table[before:]
                             )
                             self._slot_nblk[req.bt_slot] = len(req.block_table)
+                        self._release_window(req, req.num_tokens - 1)
                         i += 1
                     except RuntimeError:
                         if not self._preempt_youngest():
@@ -638,6 +667,8 @@ class LLMEngine:
                 req.prefill_pos = e
                 if final:
                     self.prefilling.remove(req)
+                else:
+                    self._release_window(req, e)  # next chunk starts at e
             final_tokens = [
                 t for t, (req, _, _, final) in zip(tokens, work)
                 if final and req.state == "running"
@@ -729,6 +760,13 @@ class LLMEngine:
                                 raise
                     break
             reqs = list(self.running)
+            if self.sliding_window and i == -1:
+                # what the previous step left below the window (the query
+                # of this step sits at ntok + inflight - 1)
+                for req in reqs:
+                    self._release_window(
+                        req, int(self._slot_ntok[req.bt_slot]) + inflight - 1
+                    )
         if i != -1:  # needed preemption while tokens were in flight
             self._flush_pending()
             return self._decode_step()

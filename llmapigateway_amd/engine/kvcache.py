@@ -46,6 +46,22 @@ class _PyBlockAllocator:
         self._free.extend(reversed(blocks))
 
 
+class _Released(int):
+    """Block-table entry of a block that release_before() gave back. As a
+    number it is block 0, an in-range id, so tables copy into the int32
+    block tables as they are; the kernels never read such an entry. As an
+    object it is told apart from the real block 0, so free() gives nothing
+    back twice."""
+
+    __slots__ = ()
+
+    def __repr__(self) -> str:
+        return "<released>"
+
+
+RELEASED = _Released(0)
+
+
 def make_block_allocator(num_blocks: int):
     try:
         from ..ops import _C  # type: ignore
@@ -165,6 +181,11 @@ class BlockManager:
                 parent = existing
                 continue
             blk = block_table[i]
+            if blk is RELEASED:
+                # given back by release_before (sliding window): the chain
+                # cannot be continued through a block this request no
+                # longer holds
+                break
             if blk in self._block_key:
                 # this block is already registered under a different chain
                 # (it IS a cached block we reused) — just walk on
@@ -180,9 +201,28 @@ class BlockManager:
         if need > 0:
             block_table.extend(self._alloc_raw(need))
 
+    def release_before(self, block_table: List[int], first_needed_token: int) -> int:
+        """Sliding window: give back every block of the table that lies
+        wholly below token position `first_needed_token`. A block shared
+        through the prefix cache is dereferenced, any other goes back to the
+        allocator. Its entry becomes RELEASED, so positions stay absolute.
+        Released entries always form a prefix of the table, which makes a
+        repeated call a no-op. Returns the number of blocks given back."""
+        n = min(max(first_needed_token, 0) // self.block_size, len(block_table))
+        first = n
+        while first > 0 and block_table[first - 1] is not RELEASED:
+            first -= 1
+        if first == n:
+            return 0
+        self.free(block_table[first:n])
+        block_table[first:n] = [RELEASED] * (n - first)
+        return n - first
+
     def free(self, block_table: List[int]) -> None:
         plain = []
         for blk in block_table:
+            if blk is RELEASED:
+                continue
             if blk in self._block_key:
                 self._unref(blk)
             else:

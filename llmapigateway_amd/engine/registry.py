@@ -133,6 +133,8 @@ class EngineRegistry:
             key += f"/kv{spec.kv_dtype}"
         if spec.weight_dtype not in ("auto", None):
             key += f"/w{spec.weight_dtype}"
+        if spec.sliding_window is not None:
+            key += f"/sw{spec.sliding_window}"
         if spec.dtype not in ("bfloat16", None):
             key += f"/{spec.dtype}"
         return key
@@ -158,6 +160,12 @@ class EngineRegistry:
                 return handle
             if spec.tp > 1:
                 from .tp_group import TPEngineClient
+
+                if spec.sliding_window is not None:
+                    raise RuntimeError(
+                        "sliding_window overrides the preset on single-GPU "
+                        "engines only; under TP the preset's window applies"
+                    )
 
                 if torch.cuda.is_available() and torch.cuda.device_count() < spec.tp:
                     raise RuntimeError(
@@ -192,6 +200,7 @@ class EngineRegistry:
                 use_hipgraph=None if self.settings.engine_use_hipgraph else False,
                 kv_dtype=spec.kv_dtype,
                 weight_dtype=spec.weight_dtype,
+                sliding_window=spec.sliding_window,
             )
             if engine.graph_runner is not None:
                 logger.info("pre-capturing decode hipGraphs for %s", key)
@@ -724,6 +733,7 @@ class EngineRegistry:
                     kv_blocks_free=eng.kv.manager.num_free_blocks,
                     kv_blocks_total=eng.kv.num_blocks,
                     kv_dtype="fp8" if eng.kv.fp8 else str(eng.dtype).replace("torch.", ""),
+                    sliding_window=eng.sliding_window,
                     prefix_cache_hits=eng.kv.manager.stats_prefix_hits,
                     prefix_cached_tokens=eng.kv.manager.stats_prefix_tokens,
                 )

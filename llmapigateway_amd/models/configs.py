@@ -7,6 +7,7 @@ Shapes match the public architectures named by BASELINE.json's configs
 from __future__ import annotations
 
 from dataclasses import dataclass, replace
+from typing import Optional
 
 
 @dataclass(frozen=True)
@@ -23,6 +24,9 @@ class ModelConfig:
     rms_eps: float = 1e-5
     max_positions: int = 8192
     tie_embeddings: bool = False
+    # sliding-window attention: a token attends to the last W positions
+    # (itself included); None = full causal attention
+    sliding_window: Optional[int] = None
 
     @property
     def q_size(self) -> int:
@@ -98,6 +102,19 @@ MODEL_PRESETS = {
         vocab_size=32000,
         rope_theta=10000.0,
     ),
+    # Mistral-7B-v0.1: the same shapes with its 4096-token sliding window
+    "mistral-7b-v0.1": ModelConfig(
+        name="mistral-7b-v0.1",
+        hidden_size=4096,
+        intermediate_size=14336,
+        num_layers=32,
+        num_heads=32,
+        num_kv_heads=8,
+        vocab_size=32000,
+        rope_theta=10000.0,
+        max_positions=32768,
+        sliding_window=4096,
+    ),
     # tiny shapes for CPU tests / smoke
     "tiny-llama": ModelConfig(
         name="tiny-llama",
@@ -110,6 +127,20 @@ MODEL_PRESETS = {
         head_dim=64,
         rope_theta=10000.0,
         max_positions=512,
+    ),
+    # tiny-llama with a sliding window (window and block-release tests)
+    "tiny-llama-swa": ModelConfig(
+        name="tiny-llama-swa",
+        hidden_size=256,
+        intermediate_size=512,
+        num_layers=2,
+        num_heads=4,
+        num_kv_heads=2,
+        vocab_size=512,
+        head_dim=64,
+        rope_theta=10000.0,
+        max_positions=512,
+        sliding_window=24,
     ),
     # tiny shape divisible for world-4 TP lockstep tests
     "tiny-llama-tp4": ModelConfig(

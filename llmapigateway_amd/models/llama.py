@@ -101,6 +101,9 @@ class LlamaModel:
         self.tp_rank = tp_rank
         self.tp_size = tp_size
         self.scale = config.head_dim ** -0.5
+        # sliding-window attention: a constant of the model (0 = none),
+        # so captured decode graphs stay valid
+        self.window = int(config.sliding_window or 0)
         self.layers: List[Dict[str, torch.Tensor]] = []
         self._init_weights(seed)
         self.cos_sin = ops.build_rope_cache(
@@ -452,6 +455,7 @@ class LlamaModel:
                     cached_lens=batch.cached_lens,
                     k_scale=ksc[i] if batch.cached_lens is not None else None,
                     v_scale=vsc[i] if batch.cached_lens is not None else None,
+                    window=self.window,
                 )
             elif batch.kind == "mixed":
                 Tp = batch.n_prefill_tokens
@@ -464,18 +468,19 @@ class LlamaModel:
                     cached_lens=batch.cached_lens,
                     k_scale=ksc[i] if batch.cached_lens is not None else None,
                     v_scale=vsc[i] if batch.cached_lens is not None else None,
+                    window=self.window,
                 )
                 attn_d = ops.attention_decode(
                     q[Tp:], k_caches[i], v_caches[i],
                     batch.dec_block_tables, batch.dec_context_lens, self.scale,
-                    k_scale=ksc[i], v_scale=vsc[i],
+                    k_scale=ksc[i], v_scale=vsc[i], window=self.window,
                 )
                 attn = torch.cat([attn_p, attn_d], dim=0)
             else:
                 attn = ops.attention_decode(
                     q, k_caches[i], v_caches[i], batch.block_tables,
                     batch.context_lens, self.scale,
-                    k_scale=ksc[i], v_scale=vsc[i],
+                    k_scale=ksc[i], v_scale=vsc[i], window=self.window,
                 )
 
             x, residual = self._row_parallel_norm(

@@ -189,13 +189,18 @@ def attention_prefill(
     cached_lens: Optional[torch.Tensor] = None,
     k_scale: Optional[torch.Tensor] = None,
     v_scale: Optional[torch.Tensor] = None,
+    window: Optional[int] = 0,
 ) -> torch.Tensor:
     """Varlen causal prefill. With cached_lens set, each sequence also
     attends (unmasked) to its first cached_lens[i] positions read from the
     paged KV cache via block_tables — the prefix-caching / chunked-prefill
-    context phase."""
+    context phase. window = W > 0 is sliding-window attention: the row at
+    absolute position p = cached_lens[i] + r attends to keys p - W < j <= p,
+    and cache blocks wholly below a sequence's first window are not read;
+    0 or None is no window."""
     if scale is None:
         scale = float(q.shape[-1]) ** -0.5
+    window = _check_window(window)
     if q.is_cuda:
         if not causal:
             raise NotImplementedError("GPU prefill kernel is causal-only")
@@ -207,14 +212,22 @@ def attention_prefill(
         _native().attention_prefill(
             out, q, k, v, cu_seqlens.int(), tile_seq, tile_off, float(scale),
             k_cache, v_cache, block_tables, cached_lens, k_scale, v_scale,
+            window,
         )
         return out
     return reference.attention_prefill(
         q, k, v, cu_seqlens, scale, causal,
         k_cache=k_cache, v_cache=v_cache,
         block_tables=block_tables, cached_lens=cached_lens,
-        k_scale=k_scale, v_scale=v_scale,
+        k_scale=k_scale, v_scale=v_scale, window=window,
     )
+
+
+def _check_window(window: Optional[int]) -> int:
+    window = int(window or 0)
+    if window < 0:
+        raise ValueError(f"window must be >= 0, got {window}")
+    return window
 
 
 _SPLIT_SPAN = 2048  # keep in sync with SPLIT_SPAN in attention_decode.hip
@@ -261,9 +274,15 @@ def attention_decode(
     scale: Optional[float] = None,
     k_scale: Optional[torch.Tensor] = None,
     v_scale: Optional[torch.Tensor] = None,
+    window: Optional[int] = 0,
 ) -> torch.Tensor:
+    """Paged single-token decode. window = W > 0 is sliding-window
+    attention over the keys [max(0, L - W), L) of each sequence: blocks
+    wholly below them are not read (nor their block-table entries), so the
+    caller may have released them; 0 or None is no window."""
     if scale is None:
         scale = float(q.shape[-1]) ** -0.5
+    window = _check_window(window)
     if q.is_cuda:
         out = torch.empty_like(q)
         # flash-decode context splits when (B x Hkv) underfills the 256 CUs
@@ -273,6 +292,11 @@ def attention_decode(
         # stays 8 and the launcher widens the span to cover the block table
         B, Hq = q.shape[0], q.shape[1]
         max_ctx = block_tables.shape[1] * k_cache.shape[2]
+        if window:
+            # the kernel measures the splits from the 64-aligned window
+            # start: at most window + 63 keys, whatever the context (a
+            # constant of the call, never context_lens: capture-stable)
+            max_ctx = min(max_ctx, window + 64)
         nsplit = 1
         if B * k_cache.shape[1] < 192 and max_ctx > _SPLIT_SPAN:
             nsplit = min(8, -(-max_ctx // _SPLIT_SPAN))
@@ -283,17 +307,18 @@ def attention_decode(
             # path engages (small-batch long-context), v2 everywhere else
             _native().attention_decode(
                 out, q, k_cache, v_cache, block_tables, context_lens,
-                float(scale), pa, pm, nsplit, k_scale, v_scale, 1,
+                float(scale), pa, pm, nsplit, k_scale, v_scale, 1, window,
             )
         else:
             _native().attention_decode(
                 out, q, k_cache, v_cache, block_tables, context_lens,
                 float(scale), None, None, 1, k_scale, v_scale, _DECODE_VER,
+                window,
             )
         return out
     return reference.attention_decode(
         q, k_cache, v_cache, block_tables, context_lens, scale,
-        k_scale=k_scale, v_scale=v_scale,
+        k_scale=k_scale, v_scale=v_scale, window=window,
     )
 
 

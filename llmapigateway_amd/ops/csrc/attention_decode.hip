@@ -56,7 +56,8 @@ __global__ void attention_decode_kernel(
     float* __restrict__ part_acc,           // [B, Hq, NSPLIT, D] (SPLIT)
     float* __restrict__ part_ml,            // [B, Hq, NSPLIT, 2] (SPLIT)
     int nsplit,
-    int split_span) {                       // keys per split (SPLIT), multiple of 64
+    int split_span,                         // keys per split (SPLIT), multiple of 64
+    int window) {                           // sliding window W (0 = none): keys [L - W, L)
     const int seq = blockIdx.x;
     const int kvh = blockIdx.y;
     const int split = SPLIT ? blockIdx.z : 0;
@@ -68,7 +69,13 @@ __global__ void attention_decode_kernel(
         for (int i = threadIdx.x; i < G * DECODE_D / 2; i += blockDim.x) o[i] = 0u;
         return;
     }
-    const int span0 = SPLIT ? split * split_span : 0;
+    // sliding window: the oldest key in use, and the 64-key chunk holding
+    // it, from which the chunk loop and the split spans are measured.
+    // Blocks wholly below key_lo may have been released: nothing of them
+    // (row, scale, block-table entry) is read. window == 0: both are 0.
+    const int key_lo = window > 0 ? max(L - window, 0) : 0;
+    const int win0 = key_lo & ~(WAVE_SIZE - 1);
+    const int span0 = win0 + (SPLIT ? split * split_span : 0);
     // idle split (an empty context idles every split): publish an empty
     // partial, so the combine kernel reads nothing stale and yields zeros
     if (SPLIT && span0 >= L) {
@@ -102,12 +109,14 @@ __global__ void attention_decode_kernel(
         q_lds[g][d] =
             bf2f(q[(size_t)seq * q_stride + (size_t)(kvh * G + g) * D + d]) * scale;
     }
+    // the 1024 staged entries start at the window's first block
     const int nblocks = (L + block_size - 1) / block_size;
-    for (int i = tid; i < nblocks && i < 1024; i += blockDim.x)
-        bt_lds[i] = block_tables[(size_t)seq * max_blocks + i];
+    const int bt0 = key_lo / block_size;
+    for (int i = tid; bt0 + i < nblocks && i < 1024; i += blockDim.x)
+        bt_lds[i] = block_tables[(size_t)seq * max_blocks + bt0 + i];
     __syncthreads();
     const int* __restrict__ bt_global = block_tables + (size_t)seq * max_blocks;
-#define BT(idx) ((idx) < 1024 ? bt_lds[(idx)] : bt_global[(idx)])
+#define BT(idx) ((idx) - bt0 < 1024 ? bt_lds[(idx) - bt0] : bt_global[(idx)])
 
     float m[G], l[G], acc[G][4];
 #pragma unroll
@@ -122,7 +131,7 @@ __global__ void attention_decode_kernel(
     const int nchunks = (span1 + WAVE_SIZE - 1) / WAVE_SIZE;
     for (int c = c0 + wave; c < nchunks; c += NWAVES) {
         const int pos = c * WAVE_SIZE + lane;
-        const bool valid = pos < span1;
+        const bool valid = pos < span1 && pos >= key_lo;
 
         // --- phase A: lane = key ---
         float s[G];
@@ -190,8 +199,9 @@ __global__ void attention_decode_kernel(
         // dwordx2 loads: half the instructions and latency batches of the
         // earlier dim-pair/dword form). Lane l covers key j + (l>>5),
         // dims (l&31)*4..+3; 8 keys per iteration = 4 loads in flight.
-        // Keys beyond the chunk have p == 0 (masked in phase A), so only
-        // the ADDRESS needs clamping to stay inside the paged cache. ---
+        // Keys beyond the chunk or below the window have p == 0 (masked in
+        // phase A), so only the ADDRESS needs clamping to stay inside the
+        // paged cache and inside the window's blocks. ---
         const int dbase = (lane & 31) * 4;
         const int khalf = lane >> 5;
 #pragma unroll 2
@@ -201,7 +211,8 @@ __global__ void attention_decode_kernel(
             float vsc[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const int pos = min(c * WAVE_SIZE + j + 2 * u + khalf, span1 - 1);
+                const int pos =
+                    max(min(c * WAVE_SIZE + j + 2 * u + khalf, span1 - 1), key_lo);
                 const int vb = BT(pos / block_size);
                 const int vo = pos % block_size;
                 const size_t vrow_i = ((size_t)vb * Hkv + kvh) * block_size + vo;
@@ -333,7 +344,8 @@ __global__ void attention_decode_v2_kernel(
     float* __restrict__ part_acc,           // [B, Hq, NSPLIT, D] (SPLIT)
     float* __restrict__ part_ml,            // [B, Hq, NSPLIT, 2] (SPLIT)
     int nsplit,
-    int split_span) {                       // keys per split (SPLIT), multiple of 64
+    int split_span,                         // keys per split (SPLIT), multiple of 64
+    int window) {                           // sliding window W (0 = none): keys [L - W, L)
     const int seq = blockIdx.x;
     const int kvh = blockIdx.y;
     const int split = SPLIT ? blockIdx.z : 0;
@@ -345,7 +357,13 @@ __global__ void attention_decode_v2_kernel(
         for (int i = threadIdx.x; i < G * DECODE_D / 2; i += blockDim.x) o[i] = 0u;
         return;
     }
-    const int span0 = SPLIT ? split * split_span : 0;
+    // sliding window: the oldest key in use, and the 64-key chunk holding
+    // it, from which the chunk loop and the split spans are measured.
+    // Blocks wholly below key_lo may have been released: nothing of them
+    // (row, scale, block-table entry) is read. window == 0: both are 0.
+    const int key_lo = window > 0 ? max(L - window, 0) : 0;
+    const int win0 = key_lo & ~(WAVE_SIZE - 1);
+    const int span0 = win0 + (SPLIT ? split * split_span : 0);
     const int tid = threadIdx.x;
     const int lane = tid & (WAVE_SIZE - 1);
     const int wave = tid >> 6;
@@ -377,12 +395,14 @@ __global__ void attention_decode_v2_kernel(
         q_lds[g][d] =
             bf2f(q[(size_t)seq * q_stride + (size_t)(kvh * G + g) * D + d]) * scale;
     }
+    // the 1024 staged entries start at the window's first block
     const int nblocks = (L + block_size - 1) / block_size;
-    for (int i = tid; i < nblocks && i < 1024; i += blockDim.x)
-        bt_lds[i] = block_tables[(size_t)seq * max_blocks + i];
+    const int bt0 = key_lo / block_size;
+    for (int i = tid; bt0 + i < nblocks && i < 1024; i += blockDim.x)
+        bt_lds[i] = block_tables[(size_t)seq * max_blocks + bt0 + i];
     __syncthreads();
     const int* __restrict__ bt_global = block_tables + (size_t)seq * max_blocks;
-#define BT2(idx) ((idx) < 1024 ? bt_lds[(idx)] : bt_global[(idx)])
+#define BT2(idx) ((idx) - bt0 < 1024 ? bt_lds[(idx) - bt0] : bt_global[(idx)])
 
     float m[HPW], l[HPW], acc[HPW][4];
 #pragma unroll
@@ -405,7 +425,7 @@ __global__ void attention_decode_v2_kernel(
             const int key = (pass << 4) | (tid >> 4);
             const int chunk = tid & 15;  // 16-B chunk 0..15
             const int pos = c * WAVE_SIZE + key;
-            const int cpos = min(pos, span1 - 1);
+            const int cpos = max(min(pos, span1 - 1), key_lo);
             const int blk = BT2(cpos / block_size);
             const size_t row =
                 ((size_t)blk * Hkv + kvh) * block_size + cpos % block_size;
@@ -447,7 +467,7 @@ __global__ void attention_decode_v2_kernel(
 
         // ---- phase A: lane = key (LDS, swizzle-matched reads) ----
         const int pos = c * WAVE_SIZE + lane;
-        const bool valid = pos < span1;
+        const bool valid = pos < span1 && pos >= key_lo;
 #pragma unroll
         for (int hh = 0; hh < HPW; ++hh) {
             const int g = wave + hh * NWAVES;
@@ -604,6 +624,7 @@ __global__ void attention_decode_v3_kernel(
         bt_lds[i] = block_tables[(size_t)seq * max_blocks + i];
     __syncthreads();
     const int* __restrict__ bt_global = block_tables + (size_t)seq * max_blocks;
+#undef BT2  // v3 has no window: its table is staged from entry 0
 #define BT2(idx) ((idx) < 1024 ? bt_lds[(idx)] : bt_global[(idx)])
 
     float m[HPW], l[HPW], acc[HPW][4];
@@ -807,9 +828,10 @@ extern "C" hipError_t launch_attention_decode(
     const float* k_scale, const float* v_scale,
     const int* block_tables, const int* context_lens, float scale, int B,
     int Hq, int Hkv, int block_size, int max_blocks, int D, int64_t q_stride,
-    float* part_acc, float* part_ml, int nsplit, int version,
+    float* part_acc, float* part_ml, int nsplit, int version, int window,
     hipStream_t stream) {
     if (D != DECODE_D) return hipErrorNotSupported;
+    if (window < 0) return hipErrorInvalidValue;
     if (Hq % Hkv != 0) return hipErrorInvalidValue;
     if (nsplit > 1 && (part_acc == nullptr || part_ml == nullptr))
         return hipErrorInvalidValue;
@@ -820,9 +842,12 @@ extern "C" hipError_t launch_attention_decode(
     // positions), else the table divided evenly, rounded up to whole
     // 64-key chunks, so that no key past nsplit * SPLIT_SPAN is dropped.
     // Derived from shapes only (never context_lens): hipGraph-capture-stable.
+    // With a sliding window the splits are measured from the 64-aligned
+    // window start and have to cover at most window + 63 keys.
     int split_span = SPLIT_SPAN;
     if (nsplit > 1) {
-        const int64_t max_ctx = (int64_t)max_blocks * block_size;
+        int64_t max_ctx = (int64_t)max_blocks * block_size;
+        if (window > 0 && (int64_t)window + 64 < max_ctx) max_ctx = (int64_t)window + 64;
         const int64_t even = ((max_ctx + nsplit - 1) / nsplit + 63) / 64 * 64;
         if (even > SPLIT_SPAN) split_span = (int)even;
     }
@@ -836,14 +861,14 @@ extern "C" hipError_t launch_attention_decode(
                     (bf16*)out, (const bf16*)q, k_cache, v_cache, k_scale,     \
                     v_scale, block_tables, context_lens, scale, Hq, Hkv,       \
                     block_size, max_blocks, q_stride, part_acc, part_ml,       \
-                    nsplit, split_span);                                       \
+                    nsplit, split_span, window);                               \
         else                                                                   \
             attention_decode_kernel<GV, SPLIT, FP8V>                           \
                 <<<grid, block, 0, stream>>>(                                  \
                     (bf16*)out, (const bf16*)q, k_cache, v_cache, k_scale,     \
                     v_scale, block_tables, context_lens, scale, Hq, Hkv,       \
                     block_size, max_blocks, q_stride, part_acc, part_ml,       \
-                    nsplit, split_span);                                       \
+                    nsplit, split_span, window);                               \
     } while (0)
 #define LAUNCH_G2(GV, SPLIT)                                                   \
     do {                                                                       \

@@ -69,7 +69,9 @@ __global__ void attention_prefill_kernel(
     const int* __restrict__ block_tables,    // [B, max_blocks] or null
     const int* __restrict__ cached_lens,     // [B] or null
     int block_size,
-    int max_blocks) {
+    int max_blocks,
+    int window) {   // sliding window W (0 = none): row at absolute position
+                    // p attends to keys p - W < j <= p
     const int tile = blockIdx.x;
     const int head = blockIdx.y;
     const int kvh = head / (Hq / Hkv);
@@ -116,12 +118,20 @@ __global__ void attention_prefill_kernel(
 #pragma unroll
     for (int d = 0; d < 8; ++d) accO[d] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    // ---- phase 0: cached context from the paged KV cache (unmasked) ----
+    // sliding window: the lowest absolute key position that any row of this
+    // q tile attends to (row tile0 sits at absolute position cached + tile0).
+    // K/V tiles wholly below it are skipped, and of the paged cache nothing
+    // below it is read: those blocks may have been released. 0 without one.
+    const int win_lo = window > 0 ? max(cached + tile0 - window + 1, 0) : 0;
+
+    // ---- phase 0: cached context from the paged KV cache (masked only by
+    // the window: cached positions precede every fresh row) ----
     const int n_cached_tiles = (cached + KVTILE - 1) / KVTILE;
     const int* bt = (block_tables != nullptr)
                         ? block_tables + (size_t)seq * max_blocks
                         : nullptr;
-    for (int jt = 0; jt < n_cached_tiles; ++jt) {
+    for (int jt = win_lo >= cached ? n_cached_tiles : win_lo / KVTILE;
+         jt < n_cached_tiles; ++jt) {
         const int key0 = jt * KVTILE;
         const int keys_here = min(KVTILE, cached - key0);
 
@@ -130,7 +140,7 @@ __global__ void attention_prefill_kernel(
             const int kk = i / (PF_D / 8);
             const int d0 = (i % (PF_D / 8)) * 8;
             uint4 kraw = {0, 0, 0, 0}, vraw = {0, 0, 0, 0};
-            if (kk < keys_here) {
+            if (kk < keys_here && key0 + kk >= win_lo) {
                 const int pos = key0 + kk;
                 const size_t row =
                     ((size_t)bt[pos / block_size] * Hkv + kvh) * block_size +
@@ -192,9 +202,11 @@ __global__ void attention_prefill_kernel(
             for (int sub = 0; sub < 4; ++sub) {
                 const int key = key0 + sub * 16 + lrow;
                 float val = s[sub][r] * scale;
-                // only key-validity masking: all cached keys precede
+                // key validity and the window: all cached keys precede
                 // every fresh q row, so no causal term
-                if (key >= cached || qrow >= seq_len) val = NEG_INF;
+                if (key >= cached || qrow >= seq_len ||
+                    (window > 0 && key <= cached + qrow - window))
+                    val = NEG_INF;
                 p_val[sub][r] = val;
                 mx = fmaxf(mx, val);
             }
@@ -242,7 +254,9 @@ __global__ void attention_prefill_kernel(
     const int kv_limit = min(seq_len, tile0 + QTILE);  // causal: keys < limit
     const int n_kv_tiles = (kv_limit + KVTILE - 1) / KVTILE;
 
-    for (int jt = 0; jt < n_kv_tiles; ++jt) {
+    // fresh key j sits at absolute position cached + j
+    const int fresh_lo = max(win_lo - cached, 0);
+    for (int jt = fresh_lo / KVTILE; jt < n_kv_tiles; ++jt) {
         const int key0 = jt * KVTILE;
         const int keys_here = min(KVTILE, kv_limit - key0);
 
@@ -291,7 +305,9 @@ __global__ void attention_prefill_kernel(
             for (int sub = 0; sub < 4; ++sub) {
                 const int key = key0 + sub * 16 + lrow;       // this lane's C col
                 float val = s[sub][r] * scale;
-                if (key > qrow || key >= seq_len || qrow >= seq_len) val = NEG_INF;
+                if (key > qrow || key >= seq_len || qrow >= seq_len ||
+                    (window > 0 && key <= qrow - window))
+                    val = NEG_INF;
                 p_val[sub][r] = val;
                 mx = fmaxf(mx, val);
             }
@@ -364,8 +380,9 @@ extern "C" hipError_t launch_attention_prefill(
     int64_t k_stride, int64_t v_stride, const void* k_cache,
     const void* v_cache, const float* k_scale, const float* v_scale,
     const int* block_tables, const int* cached_lens,
-    int block_size, int max_blocks, hipStream_t stream) {
+    int block_size, int max_blocks, int window, hipStream_t stream) {
     if (D != PF_D) return hipErrorNotSupported;
+    if (window < 0) return hipErrorInvalidValue;
     dim3 grid(ntiles, Hq);
     dim3 block(PF_WAVES * WAVE_SIZE);
     if (k_scale != nullptr)
@@ -373,13 +390,13 @@ extern "C" hipError_t launch_attention_prefill(
             (bf16*)out, (const bf16*)q, (const bf16*)k, (const bf16*)v,
             cu_seqlens, tile_seq, tile_off, scale, Hq, Hkv, q_stride, k_stride,
             v_stride, k_cache, v_cache, k_scale, v_scale, block_tables,
-            cached_lens, block_size, max_blocks);
+            cached_lens, block_size, max_blocks, window);
     else
         attention_prefill_kernel<false><<<grid, block, 0, stream>>>(
             (bf16*)out, (const bf16*)q, (const bf16*)k, (const bf16*)v,
             cu_seqlens, tile_seq, tile_off, scale, Hq, Hkv, q_stride, k_stride,
             v_stride, k_cache, v_cache, nullptr, nullptr, block_tables,
-            cached_lens, block_size, max_blocks);
+            cached_lens, block_size, max_blocks, window);
     HIP_CHECK_LAST();
     return hipSuccess;
 }

@@ -19,8 +19,8 @@ hipError_t launch_rope(void*, void*, const int64_t*, const float*, int, int64_t,
 hipError_t launch_swiglu(void*, const void*, int, int, hipStream_t);
 hipError_t launch_kv_cache_write(const void*, const void*, void*, void*, float*, float*, const int64_t*, int, int64_t, int64_t, int, int, int, hipStream_t);
 hipError_t launch_rope_kv(void*, void*, const void*, void*, void*, float*, float*, const int64_t*, const float*, const int64_t*, int, int64_t, int64_t, int64_t, int, int, int, int, hipStream_t);
-hipError_t launch_attention_decode(void*, const void*, const void*, const void*, const float*, const float*, const int*, const int*, float, int, int, int, int, int, int, int64_t, float*, float*, int, int, hipStream_t);
-hipError_t launch_attention_prefill(void*, const void*, const void*, const void*, const int*, const int*, const int*, int, float, int, int, int, int64_t, int64_t, int64_t, const void*, const void*, const float*, const float*, const int*, const int*, int, int, hipStream_t);
+hipError_t launch_attention_decode(void*, const void*, const void*, const void*, const float*, const float*, const int*, const int*, float, int, int, int, int, int, int, int64_t, float*, float*, int, int, int, hipStream_t);
+hipError_t launch_attention_prefill(void*, const void*, const void*, const void*, const int*, const int*, const int*, int, float, int, int, int, int64_t, int64_t, int64_t, const void*, const void*, const float*, const float*, const int*, const int*, int, int, int, hipStream_t);
 hipError_t launch_sample(int64_t*, const float*, const float*, const float*, float*, int*, int, int, hipStream_t);
 hipError_t launch_topk_topp_filter(float*, const float*, const int*, int, int, hipStream_t);
 }
@@ -162,7 +162,9 @@ void attention_decode(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
                       c10::optional<torch::Tensor> part_acc,
                       c10::optional<torch::Tensor> part_ml, int64_t nsplit,
                       c10::optional<torch::Tensor> k_scale,
-                      c10::optional<torch::Tensor> v_scale, int64_t version) {
+                      c10::optional<torch::Tensor> v_scale, int64_t version,
+                      int64_t window) {
+    TORCH_CHECK(window >= 0 && window <= INT32_MAX, "window must be >= 0");
     check_cache(k_cache, "k_cache");
     TORCH_CHECK((k_cache.scalar_type() == torch::kUInt8) ==
                 (k_scale.has_value() && k_scale->defined()),
@@ -195,7 +197,7 @@ void attention_decode(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
         scale_ptr(k_scale), scale_ptr(v_scale),
         block_tables.data_ptr<int>(), context_lens.data_ptr<int>(), (float)scale,
         B, Hq, Hkv, block_size, max_blocks, D, q.stride(0), pa, pm, (int)nsplit,
-        (int)version, current_stream()));
+        (int)version, (int)window, current_stream()));
 }
 
 void attention_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor k,
@@ -207,7 +209,8 @@ void attention_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor k,
                        c10::optional<torch::Tensor> block_tables,
                        c10::optional<torch::Tensor> cached_lens,
                        c10::optional<torch::Tensor> k_scale,
-                       c10::optional<torch::Tensor> v_scale) {
+                       c10::optional<torch::Tensor> v_scale, int64_t window) {
+    TORCH_CHECK(window >= 0 && window <= INT32_MAX, "window must be >= 0");
     check_bf16(q, "q");
     check_bf16(out, "out");
     TORCH_CHECK(out.is_contiguous());
@@ -242,7 +245,7 @@ void attention_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor k,
         tile_off.data_ptr<int>(), ntiles, (float)scale, q.size(1), k.size(1),
         q.size(2), q.stride(0), k.stride(0), v.stride(0), kc, vc,
         kc ? scale_ptr(k_scale) : nullptr, vc ? scale_ptr(v_scale) : nullptr,
-        bt, cl, block_size, max_blocks, current_stream()));
+        bt, cl, block_size, max_blocks, (int)window, current_stream()));
 }
 
 void sample(torch::Tensor out, torch::Tensor logits, torch::Tensor temperature,
@@ -558,8 +561,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("swiglu", &swiglu, "fused SiLU-gate multiply");
     m.def("kv_cache_write", &kv_cache_write, "paged KV cache scatter");
     m.def("rope_kv_write", &rope_kv_write, "fused RoPE + paged KV scatter");
-    m.def("attention_decode", &attention_decode, "paged decode attention");
-    m.def("attention_prefill", &attention_prefill, "varlen causal prefill attention");
+    // window (sliding-window attention) is the one defaulted argument, so
+    // every argument is named
+    m.def("attention_decode", &attention_decode, "paged decode attention",
+          py::arg("out"), py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+          py::arg("block_tables"), py::arg("context_lens"), py::arg("scale"),
+          py::arg("part_acc"), py::arg("part_ml"), py::arg("nsplit"),
+          py::arg("k_scale"), py::arg("v_scale"), py::arg("version"),
+          py::arg("window") = 0);
+    m.def("attention_prefill", &attention_prefill, "varlen causal prefill attention",
+          py::arg("out"), py::arg("q"), py::arg("k"), py::arg("v"),
+          py::arg("cu_seqlens"), py::arg("tile_seq"), py::arg("tile_off"),
+          py::arg("scale"), py::arg("k_cache"), py::arg("v_cache"),
+          py::arg("block_tables"), py::arg("cached_lens"), py::arg("k_scale"),
+          py::arg("v_scale"), py::arg("window") = 0);
     m.def("sample", &sample, "greedy / gumbel-max sampling");
     m.def("topk_topp_filter", &topk_topp_filter,
           "in-place top-k/top-p logit filtering (histogram threshold)");

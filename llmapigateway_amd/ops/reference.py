@@ -321,10 +321,21 @@ def attention_prefill(
     cached_lens: Optional[torch.Tensor] = None,
     k_scale: Optional[torch.Tensor] = None,
     v_scale: Optional[torch.Tensor] = None,
+    window: Optional[int] = None,
 ) -> torch.Tensor:
     """Varlen causal attention with GQA over fresh K/V; with cached_lens,
     each sequence also attends (unmasked) to its cached prefix gathered
-    from the paged cache (prefix caching / chunked prefill)."""
+    from the paged cache (prefix caching / chunked prefill).
+
+    window = W > 0 (sliding-window attention): the row at absolute position
+    p (cached_lens + its row index) attends to keys p - W < j <= p only,
+    across the cached prefix and the fresh tokens alike; cache blocks that
+    lie wholly below the first row's window are not read."""
+    W = int(window or 0)
+    if W < 0:
+        raise ValueError(f"window must be >= 0, got {window}")
+    if W and not causal:
+        raise ValueError("a sliding window needs causal=True")
     T, Hq, D = q.shape
     Hkv = k.shape[1]
     group = Hq // Hkv
@@ -339,10 +350,12 @@ def attention_prefill(
         ki = k[s:e].float().repeat_interleave(group, dim=1)
         vi = v[s:e].float().repeat_interleave(group, dim=1)
         nc = int(cached_lens[i]) if cached_lens is not None else 0
-        if nc > 0:
+        # first cached position inside the window of fresh row 0
+        lo = max(nc - W + 1, 0) if W else 0
+        if nc > lo:
             bs = k_cache.shape[2]
             rows_k, rows_v = [], []
-            for pos in range(nc):
+            for pos in range(lo, nc):
                 blk = int(block_tables[i, pos // bs])
                 kr = k_cache[blk, :, pos % bs, :]
                 vr = v_cache[blk, :, pos % bs, :]
@@ -360,11 +373,15 @@ def attention_prefill(
             mask = torch.triu(
                 torch.ones(L, L, dtype=torch.bool, device=q.device), diagonal=1
             )
-            if nc > 0:  # cached keys precede every fresh row: never masked
+            if nc > lo:  # cached keys precede every fresh row: never masked
                 mask = torch.cat(
-                    [torch.zeros(L, nc, dtype=torch.bool, device=q.device), mask],
+                    [torch.zeros(L, nc - lo, dtype=torch.bool, device=q.device), mask],
                     dim=1,
                 )
+            if W:  # column c is absolute key lo + c, row r absolute nc + r
+                row = torch.arange(L, device=q.device)[:, None] + nc
+                col = torch.arange(mask.shape[1], device=q.device)[None, :] + lo
+                mask = mask | (col <= row - W)
             scores.masked_fill_(mask, float("-inf"))
         p = torch.softmax(scores, dim=-1)
         out[s:e] = torch.einsum("hqk,khd->qhd", p, vi).to(q.dtype)
@@ -380,8 +397,14 @@ def attention_decode(
     scale: Optional[float] = None,
     k_scale: Optional[torch.Tensor] = None,
     v_scale: Optional[torch.Tensor] = None,
+    window: Optional[int] = None,
 ) -> torch.Tensor:
-    """Single-token decode attention over the paged KV cache."""
+    """Single-token decode attention over the paged KV cache. window = W > 0
+    (sliding-window attention) uses keys [max(0, L - W), L) only and reads
+    no block that lies wholly below them."""
+    W = int(window or 0)
+    if W < 0:
+        raise ValueError(f"window must be >= 0, got {window}")
     B, Hq, D = q.shape
     Hkv = k_cache.shape[1]
     block_size = k_cache.shape[2]
@@ -392,16 +415,19 @@ def attention_decode(
     for b in range(B):
         L = int(context_lens[b])
         nblocks = (L + block_size - 1) // block_size
-        blocks = block_tables[b, :nblocks].long()
-        # gather [L, Hkv, D]
+        lo = max(L - W, 0) if W else 0
+        b0 = lo // block_size       # first block of the window
+        lo, L = lo - b0 * block_size, L - b0 * block_size
+        blocks = block_tables[b, b0:nblocks].long()
+        # gather [L, Hkv, D], then keep [lo, L)
         if k_scale is not None:
             kd = fp8_dequantize_rows(k_cache[blocks], k_scale[blocks])
             vd = fp8_dequantize_rows(v_cache[blocks], v_scale[blocks])
-            kk = kd.permute(0, 2, 1, 3).reshape(-1, Hkv, D)[:L].float()
-            vv = vd.permute(0, 2, 1, 3).reshape(-1, Hkv, D)[:L].float()
+            kk = kd.permute(0, 2, 1, 3).reshape(-1, Hkv, D)[lo:L].float()
+            vv = vd.permute(0, 2, 1, 3).reshape(-1, Hkv, D)[lo:L].float()
         else:
-            kk = k_cache[blocks].permute(0, 2, 1, 3).reshape(-1, Hkv, D)[:L].float()
-            vv = v_cache[blocks].permute(0, 2, 1, 3).reshape(-1, Hkv, D)[:L].float()
+            kk = k_cache[blocks].permute(0, 2, 1, 3).reshape(-1, Hkv, D)[lo:L].float()
+            vv = v_cache[blocks].permute(0, 2, 1, 3).reshape(-1, Hkv, D)[lo:L].float()
         kk = kk.repeat_interleave(group, dim=1)  # [L, Hq, D]
         vv = vv.repeat_interleave(group, dim=1)
         qb = q[b].float()  # [Hq, D]
