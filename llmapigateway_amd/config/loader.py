@@ -24,7 +24,7 @@ from pathlib import Path
 from typing import Any, Dict, List, Optional, Tuple
 from urllib.parse import parse_qs, urlparse
 
-from pydantic import BaseModel, Field, ValidationError, field_validator
+from pydantic import BaseModel, Field, ValidationError, field_validator, model_validator
 
 from . import jsonc
 
@@ -33,6 +33,19 @@ logger = logging.getLogger(__name__)
 
 class ConfigError(RuntimeError):
     """Raised when a config file is missing or fails validation at load."""
+
+
+class AdapterSpec(BaseModel):
+    """One LoRA adapter of a local engine. With ``path`` the tensors come
+    from a local torch.load(weights_only=True) file; otherwise a seeded
+    synthetic adapter of ``rank`` over ``targets`` is drawn (the base models
+    are random-init too)."""
+
+    rank: Optional[int] = None
+    alpha: Optional[float] = None
+    seed: Optional[int] = None
+    targets: Optional[List[str]] = None  # None = all seven projections
+    path: Optional[str] = None
 
 
 class EngineSpec(BaseModel):
@@ -53,6 +66,22 @@ class EngineSpec(BaseModel):
     sliding_window: Optional[int] = None  # attention window; None = the preset's, 0 = off
     fail_rate: float = 0.0               # failure injection: P(request fails)
     fail_requests: Optional[int] = None  # failure injection: fail first N requests
+    # multi-LoRA: adapters resident on this engine, selected per request by
+    # the payload key "adapter"; max_loras defaults to their count
+    max_loras: int = 0
+    max_lora_rank: int = 16
+    adapters: Dict[str, AdapterSpec] = Field(default_factory=dict)
+
+    @model_validator(mode="after")
+    def _adapter_slots(self) -> "EngineSpec":
+        if self.adapters and not self.max_loras:
+            self.max_loras = len(self.adapters)
+        if len(self.adapters) > self.max_loras:
+            raise ValueError(
+                f"{len(self.adapters)} adapters configured but max_loras="
+                f"{self.max_loras}"
+            )
+        return self
 
 
 class ProviderDetails(BaseModel):

@@ -70,6 +70,8 @@ class SamplingParams:
     ignore_eos: bool = False
     logprobs: bool = False
     top_logprobs: int = 0
+    # name of a loaded LoRA adapter (LLMEngine.load_adapter); None = base model
+    adapter: Optional[str] = None
 
     @classmethod
     def from_payload(cls, payload: dict, default_max_tokens: int = 256) -> "SamplingParams":
@@ -95,6 +97,7 @@ class SamplingParams:
             stop=[s for s in stop if isinstance(s, str)],
             logprobs=bool(payload.get("logprobs")),
             top_logprobs=max(0, min(20, int(payload.get("top_logprobs") or 0))),
+            adapter=(str(payload["adapter"]) if payload.get("adapter") else None),
         )
 
 
@@ -122,6 +125,10 @@ class EngineRequest:
         self.bt_slot: Optional[int] = None  # engine block-table row (running)
         self.num_cached = 0  # prompt tokens served from the prefix cache
         self.prefill_pos = 0  # prompt tokens already written to the KV cache
+        # LoRA: slot and load uid of params.adapter, resolved by add_request
+        # and kept across preemption (-1 / 0 = base model)
+        self.adapter_slot = -1
+        self.adapter_uid = 0
         self.created = time.monotonic()
         self.enqueued: float = self.created
         self.prefill_start_time: Optional[float] = None
@@ -173,7 +180,14 @@ class LLMEngine:
         tokenizer: Optional[object] = None,
         admit_min_batch: Optional[int] = None,
         admit_max_wait: Optional[float] = None,
+        max_loras: int = 0,
+        max_lora_rank: int = 16,
     ):
+        if max_loras > 0 and tp_size > 1:
+            raise NotImplementedError(
+                "LoRA adapters (max_loras > 0) are not supported with tensor "
+                "parallelism (tp_size > 1) yet"
+            )
         full_config = get_model_config(model) if isinstance(model, str) else model
         if sliding_window is not None:
             # overrides the preset's window; 0 turns it off
@@ -213,7 +227,14 @@ class LLMEngine:
             config, device=self.device, dtype=dtype, seed=seed,
             tp_group=tp_group, tp_rank=tp_rank, tp_size=tp_size,
             full_config=full_config, weight_dtype=weight_dtype,
+            max_loras=max_loras, max_lora_rank=max_lora_rank,
         )
+        # multi-LoRA: name -> {"slot", "uid", "rank", "alpha"}; a slot is
+        # rewritten only while no request refers to it
+        self.max_loras = int(max_loras)
+        self._adapters: Dict[str, dict] = {}
+        self._lora_free = list(range(self.max_loras - 1, -1, -1))
+        self._lora_uid = itertools.count(1)
         if kv_dtype == "auto":
             kv_dtype = os.environ.get("LLMAPI_KV_DTYPE", "auto")
         if num_blocks is None:
@@ -299,6 +320,7 @@ class LLMEngine:
         self._slot_nblk = np.zeros(max_batch_size, dtype=np.int32)
         # bit0 = ignore_eos, bit1 = has stop strings
         self._slot_flags = np.zeros(max_batch_size, dtype=np.int8)
+        self._slot_adapter = np.full(max_batch_size, -1, dtype=np.int32)
 
         # optional batched token-event sink (set by the gateway registry):
         # called under the engine lock with [(req, token), ...] per step
@@ -341,11 +363,117 @@ class LLMEngine:
                 f"Prompt of {len(req.prompt_ids)} tokens exceeds max_model_len={self.max_model_len}"
             )
         with self._work:
+            name = req.params.adapter
+            if name is not None:
+                entry = self._adapters.get(name)
+                if entry is None:
+                    req.state = "failed"
+                    req.finish_reason = "error"
+                    req.error = (
+                        f"unknown LoRA adapter {name!r} (loaded: "
+                        f"{sorted(self._adapters)})"
+                    )
+                    self.stats["failed"] += 1
+                    raise ValueError(req.error)
+                req.adapter_slot, req.adapter_uid = entry["slot"], entry["uid"]
             req.enqueued = time.monotonic()
             self.waiting.append(req)
             self.stats["requests"] += 1
             self._work.notify_all()
         return req
+
+    # ---- LoRA adapters ----
+    def load_adapter(
+        self,
+        name: str,
+        tensors: Optional[Dict[str, torch.Tensor]] = None,
+        *,
+        rank: Optional[int] = None,
+        alpha: Optional[float] = None,
+        seed: Optional[int] = None,
+        targets: Optional[List[str]] = None,
+        path: Optional[str] = None,
+    ) -> None:
+        """Make adapter `name` selectable by SamplingParams.adapter.
+        `tensors` is the dict LlamaModel.set_adapter takes, `path` a local
+        torch.load(..., weights_only=True) file holding it; with neither, a
+        seeded synthetic adapter of `rank` over `targets` is drawn. Loading
+        an already loaded name replaces it (it must be idle); if that load
+        fails, the name is gone and its slot is free: the old adapter is
+        not kept half-overwritten. Takes the engine lock, which orders the
+        load against admission and the other adapter calls, not against a
+        forward in flight: what makes it safe is that the slot it writes is
+        one no waiting, prefilling or running request refers to, and that
+        the copies are stream-ordered before any later step that reads it.
+        Captured graphs hold the stacks' addresses, which do not change.
+        Every load gets a fresh uid: KV cached under an earlier load of the
+        same name is never reused."""
+        if not self.max_loras:
+            raise RuntimeError("this engine was built without adapters (max_loras=0)")
+        if tensors is None and path is not None:
+            tensors = torch.load(path, map_location="cpu", weights_only=True)
+        if tensors is None:
+            if rank is None:
+                raise ValueError("load_adapter needs tensors, path or rank")
+            tensors = self.model.random_adapter(rank, seed or 0, targets)
+        with self._work:
+            old = self._adapters.get(name)
+            if old is not None:
+                self._check_adapter_idle(name)
+                slot = old["slot"]
+            elif self._lora_free:
+                slot = self._lora_free.pop()
+            else:
+                raise RuntimeError(
+                    f"all {self.max_loras} adapter slots are in use "
+                    f"({sorted(self._adapters)}); unload one first"
+                )
+            try:
+                r = self.model.set_adapter(slot, tensors, alpha)
+            except Exception:
+                self.model.clear_adapter(slot)
+                self._adapters.pop(name, None)
+                self._lora_free.append(slot)
+                raise
+            self._adapters[name] = {
+                "slot": slot, "uid": next(self._lora_uid), "rank": r,
+                "alpha": float(alpha if alpha is not None else r),
+            }
+
+    def _check_adapter_idle(self, name: str) -> None:
+        busy = [
+            r.id
+            for r in itertools.chain(self.waiting, self.prefilling, self.running)
+            if r.params.adapter == name
+        ]
+        if busy:
+            raise RuntimeError(
+                f"adapter {name!r} is in use by {len(busy)} request(s) ({busy[:4]})"
+            )
+
+    def unload_adapter(self, name: str) -> None:
+        """Free the adapter's slot; raises while a waiting, prefilling or
+        running request refers to it."""
+        with self._work:
+            entry = self._adapters.get(name)
+            if entry is None:
+                raise KeyError(f"adapter {name!r} is not loaded")
+            self._check_adapter_idle(name)
+            del self._adapters[name]
+            self.model.clear_adapter(entry["slot"])
+            self._lora_free.append(entry["slot"])
+
+    def list_adapters(self) -> List[dict]:
+        with self._lock:
+            return [
+                {"name": n, **e}
+                for n, e in sorted(self._adapters.items(), key=lambda kv: kv[1]["slot"])
+            ]
+
+    def _prefix_root(self, req: EngineRequest) -> int:
+        """Prefix-cache chain root: KV written under an adapter load is
+        reusable under that load only."""
+        return -(1 + req.adapter_uid) if req.adapter_uid else -1
 
     def abort_request(self, req: EngineRequest) -> None:
         with self._work:
@@ -401,7 +529,9 @@ class LLMEngine:
             self.waiting.popleft()
             if self.prefix_caching:
                 req.block_table, req.num_cached = (
-                    self.kv.manager.allocate_with_prefix(req.prompt_ids)
+                    self.kv.manager.allocate_with_prefix(
+                        req.prompt_ids, root=self._prefix_root(req)
+                    )
                 )
             else:
                 req.block_table = self.kv.manager.allocate(need)
@@ -415,6 +545,7 @@ class LLMEngine:
             self._slot_last[req.bt_slot] = req.prompt_ids[-1]
             self._slot_maxt[req.bt_slot] = len(req.prompt_ids) + req.params.max_tokens
             self._slot_nblk[req.bt_slot] = len(req.block_table)
+            self._slot_adapter[req.bt_slot] = req.adapter_slot
             self._slot_flags[req.bt_slot] = (
                 (1 if req.params.ignore_eos else 0)
                 | (2 if req.params.stop else 0)
@@ -617,6 +748,18 @@ class LLMEngine:
             dec_bt_t = torch.from_numpy(d_tables).to(device)
             dec_ctx_t = torch.from_numpy((d_pos + 1).astype(np.int32)).to(device)
 
+        adapter_ids_t = None
+        if self.max_loras:
+            # one slot per row: each prompt chunk's rows, then the decode rows
+            aid = np.repeat(
+                np.fromiter((r.adapter_slot for r in reqs), dtype=np.int32,
+                            count=len(reqs)),
+                lens,
+            )
+            if nd:
+                aid = np.concatenate([aid, self._slot_adapter[d_rows]])
+            adapter_ids_t = torch.from_numpy(aid.astype(np.int32)).to(device)
+
         tile_seq, tile_off = ops.build_prefill_tiles(lens, device)
         batch = ForwardBatch(
             kind="mixed" if nd else "prefill",
@@ -633,6 +776,7 @@ class LLMEngine:
             dec_block_tables=dec_bt_t,
             dec_context_lens=dec_ctx_t,
             logits_indices=torch.from_numpy(logits_idx).to(device),
+            adapter_ids=adapter_ids_t,
         )
         self.stats["mixed_steps" if nd else "prefill_steps"] += 1
         logits = self.model.forward(
@@ -662,7 +806,10 @@ class LLMEngine:
                 # reusable. Under the lock — abort/_finish on gateway
                 # threads mutate the same refcount tables via kv.manager.
                 for req in finals:
-                    self.kv.manager.register_prefix(req.prompt_ids, req.block_table)
+                    self.kv.manager.register_prefix(
+                        req.prompt_ids, req.block_table,
+                        root=self._prefix_root(req),
+                    )
             for req, s, e, final in live:
                 req.prefill_pos = e
                 if final:
@@ -785,11 +932,16 @@ class LLMEngine:
         else:
             last_tokens = self._slot_last[slot_rows].copy()
 
+        adapter_ids = self._slot_adapter[slot_rows] if self.max_loras else None
+
         self.stats["decode_steps"] += 1
         logits = None
         if self.graph_runner is not None:
             try:
-                logits = self.graph_runner.run(last_tokens, pos, slots, tables_np, ctx)
+                logits = self.graph_runner.run(
+                    last_tokens, pos, slots, tables_np, ctx,
+                    adapter_ids=adapter_ids,
+                )
                 self.stats["graph_steps"] += 1
             except Exception:
                 logger.exception("hipGraph decode failed; falling back to eager")
@@ -808,6 +960,10 @@ class LLMEngine:
                 block_tables=torch.from_numpy(tables_np).to(device),
                 context_lens=torch.from_numpy(ctx).to(device),
                 logits_indices=None,
+                adapter_ids=(
+                    torch.from_numpy(adapter_ids).to(device)
+                    if adapter_ids is not None else None
+                ),
             )
             logits = self.model.forward(
                 batch, self.kv.k_caches, self.kv.v_caches,

@@ -54,6 +54,11 @@ class DecodeGraphRunner:
         self.h_slot_mapping = torch.full((B,), -1, dtype=torch.long, pin_memory=pin)
         self.h_block_tables = torch.zeros(B, NB, dtype=torch.int32, pin_memory=pin)
         self.h_context_lens = torch.ones(B, dtype=torch.int32, pin_memory=pin)
+        # multi-LoRA: adapter slot per row (-1 = base model, and every
+        # padding row); part of the batch only when the model has adapters
+        self.has_lora = bool(getattr(model, "max_loras", 0))
+        self.adapter_ids = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        self.h_adapter_ids = torch.full((B,), -1, dtype=torch.int32, pin_memory=pin)
 
         self.graphs: Dict[int, torch.cuda.CUDAGraph] = {}
         self.graph_logits: Dict[int, torch.Tensor] = {}
@@ -68,6 +73,7 @@ class DecodeGraphRunner:
             block_tables=self.block_tables[:b],
             context_lens=self.context_lens[:b],
             logits_indices=None,
+            adapter_ids=self.adapter_ids[:b] if self.has_lora else None,
         )
 
     def _capture(self, bucket: int) -> None:
@@ -115,6 +121,7 @@ class DecodeGraphRunner:
         slots,           # np.int64 [n]
         block_tables,    # np.int32 [n, <=max_blocks]
         context_lens,    # np.int32 [n]
+        adapter_ids=None,  # np.int32 [n] adapter slots; None = all base (-1)
     ) -> torch.Tensor:
         n = len(tokens)
         bucket = self.bucket_for(n)
@@ -139,6 +146,12 @@ class DecodeGraphRunner:
         self.slot_mapping[:bucket].copy_(self.h_slot_mapping[:bucket], non_blocking=True)
         self.context_lens[:bucket].copy_(self.h_context_lens[:bucket], non_blocking=True)
         self.block_tables[:bucket].copy_(self.h_block_tables[:bucket], non_blocking=True)
+        if self.has_lora:
+            ai = self.h_adapter_ids.numpy()
+            ai[:bucket] = -1
+            if adapter_ids is not None:
+                ai[:n] = adapter_ids
+            self.adapter_ids[:bucket].copy_(self.h_adapter_ids[:bucket], non_blocking=True)
 
         if bucket not in self.graphs:
             self._capture(bucket)

@@ -137,11 +137,15 @@ class BlockManager:
         if self._refs[blk] == 0:
             self._evictable[blk] = None  # LRU tail (data stays resident)
 
-    def allocate_with_prefix(self, prompt_ids) -> tuple:
-        """Returns (block_table, num_cached_tokens)."""
+    def allocate_with_prefix(self, prompt_ids, root: int = -1) -> tuple:
+        """Returns (block_table, num_cached_tokens). `root` replaces the
+        chain's initial parent: chains of different roots never meet, so KV
+        written under one root (a LoRA adapter: the engine passes
+        -(1 + uid)) is not reused under another. Block ids are >= 0, so a
+        negative root cannot collide with a parent block."""
         bs = self.block_size
         cached: List[int] = []
-        parent = -1
+        parent = root
         max_full = (len(prompt_ids) - 1) // bs  # leave >= 1 token to prefill
         for i in range(max_full):
             blk = self._table.get(self._chunk_key(parent, prompt_ids, i))
@@ -167,13 +171,16 @@ class BlockManager:
             self.stats_prefix_tokens += len(cached) * bs
         return cached + private, len(cached) * bs
 
-    def register_prefix(self, prompt_ids, block_table: List[int]) -> None:
+    def register_prefix(
+        self, prompt_ids, block_table: List[int], root: int = -1
+    ) -> None:
         """Register a request's FULL prompt blocks (KV now written) so later
-        prompts can reuse them. Call after the prefill forward is issued."""
+        prompts can reuse them. Call after the prefill forward is issued.
+        `root`: as for allocate_with_prefix."""
         if not self.prefix_caching:
             return
         bs = self.block_size
-        parent = -1
+        parent = root
         for i in range(len(prompt_ids) // bs):
             key = self._chunk_key(parent, prompt_ids, i)
             existing = self._table.get(key)

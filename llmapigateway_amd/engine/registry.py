@@ -17,6 +17,7 @@ set_failure() (exposed by the admin API route).
 from __future__ import annotations
 
 import asyncio
+import hashlib
 import json
 import logging
 import threading
@@ -137,6 +138,17 @@ class EngineRegistry:
             key += f"/sw{spec.sliding_window}"
         if spec.dtype not in ("bfloat16", None):
             key += f"/{spec.dtype}"
+        if spec.max_loras:
+            # adapters are part of what the engine serves: another adapter
+            # set is another engine
+            blob = json.dumps(
+                {n: a.model_dump() for n, a in sorted(spec.adapters.items())},
+                sort_keys=True,
+            )
+            key += (
+                f"/lora{spec.max_loras}r{spec.max_lora_rank}-"
+                f"{hashlib.sha1(blob.encode()).hexdigest()[:8]}"
+            )
         return key
 
     def _resolve_device(self, spec: EngineSpec) -> str:
@@ -161,6 +173,11 @@ class EngineRegistry:
             if spec.tp > 1:
                 from .tp_group import TPEngineClient
 
+                if spec.max_loras:
+                    raise RuntimeError(
+                        "LoRA adapters (max_loras > 0) are not supported "
+                        "with tensor parallelism (tp > 1) yet"
+                    )
                 if spec.sliding_window is not None:
                     raise RuntimeError(
                         "sliding_window overrides the preset on single-GPU "
@@ -201,7 +218,16 @@ class EngineRegistry:
                 kv_dtype=spec.kv_dtype,
                 weight_dtype=spec.weight_dtype,
                 sliding_window=spec.sliding_window,
+                max_loras=spec.max_loras,
+                max_lora_rank=spec.max_lora_rank,
             )
+            # adapters go in before the graphs are captured (a later
+            # load_adapter into a free slot is served by the same graphs)
+            for name, a in spec.adapters.items():
+                engine.load_adapter(
+                    name, rank=a.rank, alpha=a.alpha, seed=a.seed,
+                    targets=a.targets, path=a.path,
+                )
             if engine.graph_runner is not None:
                 logger.info("pre-capturing decode hipGraphs for %s", key)
                 engine.graph_runner.capture_all()
@@ -734,6 +760,7 @@ class EngineRegistry:
                     kv_blocks_total=eng.kv.num_blocks,
                     kv_dtype="fp8" if eng.kv.fp8 else str(eng.dtype).replace("torch.", ""),
                     sliding_window=eng.sliding_window,
+                    adapters=eng.list_adapters(),
                     prefix_cache_hits=eng.kv.manager.stats_prefix_hits,
                     prefix_cached_tokens=eng.kv.manager.stats_prefix_tokens,
                 )

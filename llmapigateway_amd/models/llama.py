@@ -21,6 +21,12 @@ path the slab reduction, residual add and norm are one kernel. The other hot
 ops (rope, attention, sampling) are the hand-written CDNA4 kernels behind
 llmapigateway_amd.ops.
 
+Multi-LoRA: with ``max_loras > 0`` the model holds that many adapter slots
+per layer and projection (ops.LoraStack) and adds ``ForwardBatch.adapter_ids``'
+per-row delta after each projection GEMM (ops.lora_add, ops/csrc/lora.hip);
+o/down then run linear + delta + rmsnorm_residual and gate_up linear + delta
++ swiglu, not the fused ops (see forward()).
+
 Tensor parallelism: construct with ``tp_group`` + a config pre-sharded via
 ModelConfig.scaled_for_tp; qkv/gate_up are column-sharded, o/down
 row-sharded with an RCCL all-reduce over xGMI after each (2 per layer).
@@ -66,6 +72,9 @@ class ForwardBatch:
     n_prefill_tokens: int = 0
     dec_block_tables: Optional[torch.Tensor] = None  # [Bd, max_blocks] int32
     dec_context_lens: Optional[torch.Tensor] = None  # [Bd] int32
+    # multi-LoRA: adapter slot of every row of the flat batch (-1 = base
+    # model); None = all base. Read only by a model built with max_loras > 0
+    adapter_ids: Optional[torch.Tensor] = None       # [T] int32
 
 
 class LlamaModel:
@@ -80,6 +89,8 @@ class LlamaModel:
         tp_size: int = 1,
         full_config: Optional[ModelConfig] = None,
         weight_dtype: str = "auto",
+        max_loras: int = 0,
+        max_lora_rank: int = 16,
     ):
         if weight_dtype not in ("auto", "fp8", "mxfp4"):
             raise ValueError(
@@ -105,7 +116,21 @@ class LlamaModel:
         # so captured decode graphs stay valid
         self.window = int(config.sliding_window or 0)
         self.layers: List[Dict[str, torch.Tensor]] = []
+        # multi-LoRA: max_loras adapter slots resident next to the base
+        # weights (0 = none: nothing is allocated and forward() is the
+        # adapter-free code). Set before the weights: _build_twins reads it
+        self.max_loras = int(max_loras)
         self._init_weights(seed)
+        self.lora_layers: List[Dict[str, "ops.LoraStack"]] = []
+        if self.max_loras < 0:
+            raise ValueError(f"max_loras must be >= 0, got {max_loras}")
+        if self.max_loras:
+            if tp_size > 1:
+                raise NotImplementedError(
+                    "LoRA adapters (max_loras > 0) are not supported with "
+                    "tensor parallelism (tp_size > 1) yet"
+                )
+            self._init_lora_stacks(int(max_lora_rank))
         self.cos_sin = ops.build_rope_cache(
             config.max_positions, config.head_dim, config.rope_theta, device=self.device
         )
@@ -325,6 +350,7 @@ class LlamaModel:
                         # plain twin — don't hold both in HBM
                         and not (
                             name == "gate_up"
+                            and not getattr(self, "max_loras", 0)
                             and ops._m256_swiglu_config(
                                 256, w.shape[0], w.shape[1]
                             )
@@ -335,6 +361,9 @@ class LlamaModel:
                 gu = layer["gate_up"]
                 if (
                     not legacy
+                    # with adapters resident gate_up never takes the fused
+                    # swiglu route (forward()): its twin would be dead HBM
+                    and not getattr(self, "max_loras", 0)
                     and ops._m256_swiglu_config(256, gu.shape[0], gu.shape[1])
                     is not None
                 ):
@@ -343,6 +372,139 @@ class LlamaModel:
                     layer["gate_up_int"] = ops.swizzle_weight_frag(
                         ops.interleave_gate_up(gu)
                     )
+
+    # ---- LoRA adapters ----
+    # PEFT target -> (fused projection, segment within it)
+    LORA_TARGETS = {
+        "q_proj": ("qkv", 0), "k_proj": ("qkv", 1), "v_proj": ("qkv", 2),
+        "o_proj": ("o", 0), "gate_proj": ("gate_up", 0),
+        "up_proj": ("gate_up", 1), "down_proj": ("down", 0),
+    }
+
+    def _lora_shapes(self) -> Dict[str, tuple]:
+        """projection -> (K, segment widths). gate_up is [gate; up] stacked:
+        with adapters resident it always takes the plain linear route."""
+        c = self.config
+        return {
+            "qkv": (c.hidden_size, (c.q_size, c.kv_size, c.kv_size)),
+            "o": (c.q_size, (c.hidden_size,)),
+            "gate_up": (c.hidden_size, (c.intermediate_size, c.intermediate_size)),
+            "down": (c.intermediate_size, (c.hidden_size,)),
+        }
+
+    def _init_lora_stacks(self, max_rank: int) -> None:
+        """Slot stacks for every layer and projection, allocated once (a
+        captured decode graph holds their addresses) and zero: an empty slot
+        adds nothing. Per slot: true rank (the kernels stop there) and
+        alpha / r, shared by all stacks."""
+        S, R = self.max_loras, ops.lora_padded_rank(max_rank)
+        self.max_lora_rank = R
+        dev = self.device
+        self.lora_ranks = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.lora_scales = torch.zeros(S, dtype=torch.float32, device=dev)
+        for _ in self.layers:
+            stacks = {}
+            for name, (K, widths) in self._lora_shapes().items():
+                bounds = [sum(widths[: i + 1]) for i in range(len(widths))]
+                stacks[name] = ops.LoraStack(
+                    torch.zeros(S, len(widths) * R, K, dtype=self.dtype, device=dev),
+                    torch.zeros(S, bounds[-1], R, dtype=self.dtype, device=dev),
+                    self.lora_ranks, self.lora_scales, bounds,
+                )
+            self.lora_layers.append(stacks)
+
+    def lora_bytes(self) -> int:
+        return sum(
+            t.numel() * t.element_size()
+            for stacks in self.lora_layers
+            for st in stacks.values()
+            for t in (st.A, st.B)
+        )
+
+    @torch.inference_mode()
+    def set_adapter(
+        self, slot: int, tensors: Dict[str, torch.Tensor],
+        alpha: Optional[float] = None,
+    ) -> int:
+        """Pack one adapter into slot `slot` of every stack, in place.
+        `tensors` is PEFT-style: "layers.<i>.<target>.lora_A" [r, K] and
+        "layers.<i>.<target>.lora_B" [N_part, r] for target in q_proj,
+        k_proj, v_proj, o_proj, gate_proj, up_proj, down_proj; a missing
+        target contributes zero. The fused projections stack their targets'
+        A along the segment axis and B along the output columns. alpha
+        defaults to r (scale 1). Returns r."""
+        if not (0 <= slot < self.max_loras):
+            raise ValueError(f"adapter slot {slot} outside [0, {self.max_loras})")
+        ranks = {t.shape[0] for k, t in tensors.items() if k.endswith(".lora_A")}
+        if len(ranks) != 1:
+            raise ValueError(f"an adapter needs one rank for all targets, got {sorted(ranks)}")
+        r = ranks.pop()
+        R = self.max_lora_rank
+        if not (1 <= r <= R):
+            raise ValueError(f"adapter rank {r} outside [1, max_lora_rank={R}]")
+        known = set()
+        shapes = self._lora_shapes()
+        for i, stacks in enumerate(self.lora_layers):
+            for st in stacks.values():
+                st.A[slot].zero_()
+                st.B[slot].zero_()
+            for target, (name, seg) in self.LORA_TARGETS.items():
+                ka, kb = (f"layers.{i}.{target}.lora_{x}" for x in "AB")
+                if ka not in tensors and kb not in tensors:
+                    continue
+                known.update((ka, kb))
+                a, b = tensors[ka], tensors[kb]
+                K, widths = shapes[name]
+                lo = sum(widths[:seg])
+                if tuple(a.shape) != (r, K) or tuple(b.shape) != (widths[seg], r):
+                    raise ValueError(
+                        f"layers.{i}.{target}: expected lora_A {(r, K)} and "
+                        f"lora_B {(widths[seg], r)}, got {tuple(a.shape)} and "
+                        f"{tuple(b.shape)}"
+                    )
+                st = stacks[name]
+                st.A[slot, seg * R : seg * R + r].copy_(a)
+                st.B[slot, lo : lo + widths[seg], :r].copy_(b)
+        unknown = set(tensors) - known
+        if unknown:
+            raise ValueError(f"unknown adapter tensors: {sorted(unknown)[:4]}")
+        self.lora_ranks[slot] = r
+        self.lora_scales[slot] = float(alpha if alpha is not None else r) / r
+        return r
+
+    def clear_adapter(self, slot: int) -> None:
+        """Empty a slot: rank 0, so its rows add nothing."""
+        self.lora_ranks[slot] = 0
+        self.lora_scales[slot] = 0.0
+
+    def random_adapter(
+        self, rank: int, seed: int = 0, targets: Optional[List[str]] = None
+    ) -> Dict[str, torch.Tensor]:
+        """A seeded synthetic adapter in set_adapter's layout (the base model
+        is random-init too). Both factors are N(0, 0.02), lora_B included,
+        so the adapter moves the logits visibly."""
+        targets = list(self.LORA_TARGETS) if targets is None else list(targets)
+        bad = [t for t in targets if t not in self.LORA_TARGETS]
+        if bad:
+            raise ValueError(f"unknown LoRA targets {bad}")
+        gen = torch.Generator().manual_seed(seed)
+        shapes = self._lora_shapes()
+        out: Dict[str, torch.Tensor] = {}
+        for i in range(len(self.layers)):
+            for target in targets:
+                name, seg = self.LORA_TARGETS[target]
+                K, widths = shapes[name]
+                out[f"layers.{i}.{target}.lora_A"] = torch.empty(rank, K).normal_(
+                    0.0, 0.02, generator=gen)
+                out[f"layers.{i}.{target}.lora_B"] = torch.empty(
+                    widths[seg], rank).normal_(0.0, 0.02, generator=gen)
+        return out
+
+    def _linear_lora(self, x, layer, name: str, stacks, adapter_ids) -> torch.Tensor:
+        """Base projection, then the per-row adapter delta on its bf16
+        output: the same on every weight_dtype route."""
+        y = self._linear(x, layer, name)
+        return ops.lora_add(y, x, stacks[name], adapter_ids)
 
     def param_bytes(self) -> int:
         tensors = [self.embed, self.final_norm]
@@ -421,8 +583,25 @@ class LlamaModel:
         v_scales: "Optional[List[torch.Tensor]]" = None,
     ) -> torch.Tensor:
         """Returns logits [B, vocab] at batch.logits_indices. With
-        k_scales/v_scales the caches are fp8 e4m3 (per-row scales)."""
+        k_scales/v_scales the caches are fp8 e4m3 (per-row scales).
+
+        A model built with max_loras > 0 adds batch.adapter_ids' adapter
+        delta after each of the four projection GEMMs (ops.lora_add), and
+        then o and down run linear + delta + ops.rmsnorm_residual instead
+        of the fused GEMM+norm op, and gate_up runs linear + delta +
+        ops.swiglu instead of the fused swiglu GEMM: the price of adapters
+        being resident, paid by base rows too
+        (profiles/r10_multi_lora.md)."""
         c = self.config
+        stacks_all = self.lora_layers if self.max_loras else None
+        aid = None
+        if stacks_all is not None:
+            aid = batch.adapter_ids
+            if aid is None:
+                aid = torch.full(
+                    (batch.token_ids.shape[0],), -1, dtype=torch.int32,
+                    device=self.device,
+                )
         ksc = k_scales if k_scales is not None else [None] * len(self.layers)
         vsc = v_scales if v_scales is not None else [None] * len(self.layers)
         h = F.embedding(batch.token_ids, self.embed)
@@ -434,7 +613,11 @@ class LlamaModel:
 
         for i, layer in enumerate(self.layers):
 
-            qkv = self._linear(x, layer, "qkv")
+            lora = stacks_all[i] if stacks_all is not None else None
+            if lora is None:
+                qkv = self._linear(x, layer, "qkv")
+            else:
+                qkv = self._linear_lora(x, layer, "qkv", lora, aid)
             q, k, v = qkv.split([c.q_size, c.kv_size, c.kv_size], dim=-1)
             q = q.view(T, c.num_heads, c.head_dim)
             k = k.view(T, c.num_kv_heads, c.head_dim)
@@ -483,13 +666,26 @@ class LlamaModel:
                     k_scale=ksc[i], v_scale=vsc[i], window=self.window,
                 )
 
-            x, residual = self._row_parallel_norm(
-                attn.reshape(T, c.q_size), layer, "o",
-                residual, layer["post_norm"],
-            )
             next_norm = (
                 self.layers[i + 1]["input_norm"] if i + 1 < n_layers
                 else self.final_norm
+            )
+            if lora is not None:
+                x, residual = ops.rmsnorm_residual(
+                    self._linear_lora(
+                        attn.reshape(T, c.q_size), layer, "o", lora, aid
+                    ),
+                    residual, layer["post_norm"], c.rms_eps,
+                )
+                act = ops.swiglu(self._linear_lora(x, layer, "gate_up", lora, aid))
+                x, residual = ops.rmsnorm_residual(
+                    self._linear_lora(act, layer, "down", lora, aid),
+                    residual, next_norm, c.rms_eps,
+                )
+                continue
+            x, residual = self._row_parallel_norm(
+                attn.reshape(T, c.q_size), layer, "o",
+                residual, layer["post_norm"],
             )
             if self.weight_dtype != "auto":
                 act = ops.swiglu(self._linear(x, layer, "gate_up"))

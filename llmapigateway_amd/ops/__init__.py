@@ -1142,6 +1142,111 @@ def linear_w4_rmsnorm_residual(
     return rmsnorm_residual(linear_w4(x, q_frag, s_frag, nsk), residual, norm_w, eps)
 
 
+# ---- multi-LoRA: batched-gather adapter kernels (csrc/lora.hip) ----
+LORA_MAX_RANK = 64  # keep in sync with LORA_MAX_R in lora.hip
+
+
+def lora_padded_rank(rank: int) -> int:
+    """The stack width R for adapters of up to `rank`: the next multiple
+    of 8 (one 16-byte vector of a B row), at most LORA_MAX_RANK."""
+    if not (1 <= rank <= LORA_MAX_RANK):
+        raise ValueError(f"LoRA rank must be in [1, {LORA_MAX_RANK}], got {rank}")
+    return -(-rank // 8) * 8
+
+
+class LoraStack:
+    """The adapter slots of ONE projection: A [S, nseg*R, K] and B [S, N, R]
+    in the activation dtype, zero where a slot is empty or its adapter's
+    rank is below R. ranks (int32 [S], true rank per slot) and scales (fp32
+    [S], alpha / r) are shared by all stacks of a model. seg_bounds are the
+    end columns of the nseg output segments (q | k | v, gate | up); the
+    last is N. Allocated once: captured graphs hold these addresses."""
+
+    def __init__(self, A, B, ranks, scales, seg_bounds):
+        self.A, self.B, self.ranks, self.scales = A, B, ranks, scales
+        self.seg_bounds = tuple(int(b) for b in seg_bounds)
+        self.nseg = len(self.seg_bounds)
+        self.R = B.shape[2]
+        if A.shape[1] != self.nseg * self.R or self.seg_bounds[-1] != B.shape[1]:
+            raise ValueError("LoraStack: A/B/seg_bounds do not fit together")
+
+
+_lora_t = _Scratch(torch.float32)  # shrink output t between the two kernels
+
+
+def _lora_gpu_check(t: torch.Tensor, what: str, dtype: torch.dtype) -> None:
+    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError(
+            f"LoRA ops on GPU need {what} as a contiguous {dtype} GPU tensor "
+            f"(got device={t.device}, dtype={t.dtype}, "
+            f"contiguous={t.is_contiguous()})"
+        )
+
+
+def lora_shrink(
+    x: torch.Tensor, A: torch.Tensor, ranks: torch.Tensor,
+    adapter_ids: torch.Tensor, nseg: int, out: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """t [T, nseg*R] fp32 with t[row, s*R + j] = sum_k x[row, k] *
+    A[slot, s*R + j, k], slot = adapter_ids[row]. On the GPU a row of slot
+    -1 and the columns j >= ranks[slot] are NOT written (lora_expand reads
+    neither); t is `out` when given, else a view of the per-device scratch,
+    valid until the next call. CPU: the reference, which zeroes them."""
+    if not x.is_cuda:
+        t = reference.lora_shrink(x, A, ranks, adapter_ids, nseg)
+        if out is not None:
+            out.copy_(t)
+            return out
+        return t
+    _lora_gpu_check(x, "x", torch.bfloat16)
+    _lora_gpu_check(A, "A", torch.bfloat16)
+    _lora_gpu_check(ranks, "ranks", torch.int32)
+    _lora_gpu_check(adapter_ids, "adapter_ids", torch.int32)
+    T, nR = x.shape[0], A.shape[1]
+    if out is None:
+        out = _lora_t.get(x.device, T * nR)[: T * nR].view(T, nR)
+    _native().lora_shrink(out, x, A, ranks, adapter_ids, int(nseg))
+    return out
+
+
+def lora_expand(
+    y: torch.Tensor, t: torch.Tensor, B: torch.Tensor, ranks: torch.Tensor,
+    scales: torch.Tensor, adapter_ids: torch.Tensor, seg_bounds,
+) -> torch.Tensor:
+    """In place on y [T, N]: y[row, n] = bf16(float(y[row, n]) +
+    scales[slot] * sum_j t[row, seg(n)*R + j] * B[slot, n, j]); a row of
+    slot -1 keeps its bits. seg_bounds: end column of each segment (up to
+    three, multiples of 8, the last one N). Returns y."""
+    seg_bounds = tuple(int(b) for b in seg_bounds)
+    N = y.shape[1]
+    if not (1 <= len(seg_bounds) <= 3) or seg_bounds[-1] != N:
+        raise ValueError(f"seg_bounds {seg_bounds} must be 1-3 ends, the last {N}")
+    if not y.is_cuda:
+        return reference.lora_expand(y, t, B, ranks, scales, adapter_ids, seg_bounds)
+    _lora_gpu_check(y, "y", torch.bfloat16)
+    _lora_gpu_check(B, "B", torch.bfloat16)
+    _lora_gpu_check(t, "t", torch.float32)
+    _lora_gpu_check(ranks, "ranks", torch.int32)
+    _lora_gpu_check(scales, "scales", torch.float32)
+    _lora_gpu_check(adapter_ids, "adapter_ids", torch.int32)
+    starts = seg_bounds[:-1] + (N, N)  # a segment that is not there starts at N
+    _native().lora_expand(
+        y, t, B, ranks, scales, adapter_ids, len(seg_bounds), starts[0], starts[1]
+    )
+    return y
+
+
+def lora_add(
+    y: torch.Tensor, x: torch.Tensor, stack: LoraStack, adapter_ids: torch.Tensor
+) -> torch.Tensor:
+    """y += scale * B (A x) per row, in place on the projection's output y
+    = W x: lora_shrink then lora_expand over one projection's stack."""
+    t = lora_shrink(x, stack.A, stack.ranks, adapter_ids, stack.nseg)
+    return lora_expand(
+        y, t, stack.B, stack.ranks, stack.scales, adapter_ids, stack.seg_bounds
+    )
+
+
 def topk_topp_filter(
     logits: torch.Tensor, topp: torch.Tensor, topk: torch.Tensor
 ) -> torch.Tensor:
@@ -1201,6 +1306,11 @@ __all__ = [
     "gemm_w4_m256",
     "gemm_w4_m256_rmsnorm_residual",
     "dequant_w4",
+    "LoraStack",
+    "lora_padded_rank",
+    "lora_shrink",
+    "lora_expand",
+    "lora_add",
     "attention_prefill",
     "attention_decode",
     "sample",

@@ -23,6 +23,8 @@ hipError_t launch_attention_decode(void*, const void*, const void*, const void*,
 hipError_t launch_attention_prefill(void*, const void*, const void*, const void*, const int*, const int*, const int*, int, float, int, int, int, int64_t, int64_t, int64_t, const void*, const void*, const float*, const float*, const int*, const int*, int, int, int, hipStream_t);
 hipError_t launch_sample(int64_t*, const float*, const float*, const float*, float*, int*, int, int, hipStream_t);
 hipError_t launch_topk_topp_filter(float*, const float*, const int*, int, int, hipStream_t);
+hipError_t launch_lora_shrink(float*, const void*, const void*, const int*, const int*, int, int, int, int, int, hipStream_t);
+hipError_t launch_lora_expand(void*, const float*, const void*, const int*, const float*, const int*, int, int, int, int, int, int, int, hipStream_t);
 }
 
 namespace {
@@ -552,9 +554,84 @@ void dequant_w4(torch::Tensor out, torch::Tensor q_frag, torch::Tensor s_frag) {
                                 s_frag.data_ptr(), N, K, current_stream()));
 }
 
+// per-slot / per-row int32 metadata of the LoRA kernels
+void check_lora_meta(const torch::Tensor& ranks, const torch::Tensor& adapter_ids,
+                     int64_t S, int64_t T) {
+    TORCH_CHECK(ranks.is_cuda() && adapter_ids.is_cuda(),
+                "ranks/adapter_ids must be on GPU");
+    TORCH_CHECK(ranks.scalar_type() == torch::kInt32 && ranks.is_contiguous() &&
+                ranks.numel() == S, "ranks must be int32 [S]");
+    TORCH_CHECK(adapter_ids.scalar_type() == torch::kInt32 &&
+                adapter_ids.is_contiguous() && adapter_ids.numel() == T,
+                "adapter_ids must be int32 [T]");
+}
+
+void lora_shrink(torch::Tensor t, torch::Tensor x, torch::Tensor A,
+                 torch::Tensor ranks, torch::Tensor adapter_ids, int64_t nseg) {
+    check_bf16(x, "x");
+    check_bf16(A, "A");
+    TORCH_CHECK(x.is_contiguous() && A.is_contiguous() && t.is_contiguous());
+    TORCH_CHECK(x.dim() == 2 && A.dim() == 3 && t.dim() == 2);
+    const int64_t T = x.size(0), K = x.size(1), S = A.size(0);
+    TORCH_CHECK(nseg >= 1 && nseg <= 3, "nseg must be 1, 2 or 3");
+    TORCH_CHECK(A.size(2) == K, "A must be [S, nseg*R, K]");
+    TORCH_CHECK(A.size(1) % nseg == 0, "A rows must be nseg * R");
+    const int64_t R = A.size(1) / nseg;
+    TORCH_CHECK(R >= 8 && R <= 64 && R % 8 == 0,
+                "R must be a multiple of 8, at most 64");
+    TORCH_CHECK(K % 64 == 0 && K <= 32768,
+                "K must be a multiple of 64, at most 32768");
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+                t.size(0) == T && t.size(1) == nseg * R,
+                "t must be fp32 [T, nseg*R]");
+    check_lora_meta(ranks, adapter_ids, S, T);
+    CHECK_HIP(launch_lora_shrink(t.data_ptr<float>(), x.data_ptr(), A.data_ptr(),
+                                 ranks.data_ptr<int>(),
+                                 adapter_ids.data_ptr<int>(), (int)T, (int)S,
+                                 (int)R, (int)nseg, (int)K, current_stream()));
+}
+
+// b1/b2: first column of segment 1 / 2 (N where the segment does not exist)
+void lora_expand(torch::Tensor y, torch::Tensor t, torch::Tensor B,
+                 torch::Tensor ranks, torch::Tensor scales,
+                 torch::Tensor adapter_ids, int64_t nseg, int64_t b1,
+                 int64_t b2) {
+    check_bf16(y, "y");
+    check_bf16(B, "B");
+    TORCH_CHECK(y.is_contiguous() && B.is_contiguous() && t.is_contiguous());
+    TORCH_CHECK(y.dim() == 2 && B.dim() == 3 && t.dim() == 2);
+    const int64_t T = y.size(0), N = y.size(1), S = B.size(0), R = B.size(2);
+    TORCH_CHECK(B.size(1) == N, "B must be [S, N, R]");
+    TORCH_CHECK(N % 64 == 0, "N must be a multiple of 64");
+    TORCH_CHECK(R >= 8 && R <= 64 && R % 8 == 0,
+                "R must be a multiple of 8, at most 64");
+    TORCH_CHECK(nseg >= 1 && nseg <= 3, "nseg must be 1, 2 or 3");
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+                t.size(0) == T && t.size(1) == nseg * R,
+                "t must be fp32 [T, nseg*R]");
+    TORCH_CHECK(0 < b1 && b1 <= b2 && b2 <= N && b1 % 8 == 0 && b2 % 8 == 0,
+                "segment bounds must be ascending multiples of 8 within N");
+    TORCH_CHECK((nseg >= 2 || b1 == N) && (nseg >= 3 || b2 == N),
+                "a segment that does not exist starts at N");
+    TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == torch::kFloat32 &&
+                scales.is_contiguous() && scales.numel() == S,
+                "scales must be fp32 [S]");
+    check_lora_meta(ranks, adapter_ids, S, T);
+    CHECK_HIP(launch_lora_expand(y.data_ptr(), t.data_ptr<float>(), B.data_ptr(),
+                                 ranks.data_ptr<int>(), scales.data_ptr<float>(),
+                                 adapter_ids.data_ptr<int>(), (int)T, (int)S,
+                                 (int)R, (int)nseg, (int)N, (int)b1, (int)b2,
+                                 current_stream()));
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    m.def("lora_shrink", &lora_shrink,
+          "batched-gather LoRA shrink t = x @ A[slot].T (fp32), slot per row");
+    m.def("lora_expand", &lora_expand,
+          "batched-gather LoRA expand y += scale[slot] * t @ B[slot].T in "
+          "place, slot per row");
     m.def("rmsnorm", &rmsnorm, "RMSNorm (gfx950)");
     m.def("rmsnorm_residual", &rmsnorm_residual, "fused residual-add RMSNorm");
     m.def("rope_inplace", &rope_inplace, "rotate-half RoPE in place");

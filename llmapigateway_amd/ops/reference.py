@@ -83,6 +83,57 @@ def swiglu(x: torch.Tensor) -> torch.Tensor:
     return (g * torch.sigmoid(g) * u).to(x.dtype)
 
 
+# ---- multi-LoRA: y = W x + scale * B (A x), adapter slot per row ----
+# A [S, nseg*R, K], B [S, N, R]; ranks int32 [S] (true rank of a slot, the
+# rest of R is zero padding), scales fp32 [S] (alpha / r), adapter_ids int32
+# [T] (-1 = base model). seg_bounds are the END columns of the nseg output
+# segments (the last one is N): segment s of y reads rows [s*R, (s+1)*R) of t.
+
+def lora_shrink(
+    x: torch.Tensor, A: torch.Tensor, ranks: torch.Tensor,
+    adapter_ids: torch.Tensor, nseg: int,
+) -> torch.Tensor:
+    """t[row, s*R + j] = sum_k x[row, k] * A[slot, s*R + j, k] in fp32;
+    zero for j >= rank[slot] and for rows of slot -1 (the GPU kernel does
+    not write those)."""
+    T = x.shape[0]
+    R = A.shape[1] // nseg
+    t = torch.zeros(T, nseg * R, dtype=torch.float32, device=x.device)
+    live = (torch.arange(R, device=x.device).unsqueeze(0)
+            < ranks.to(torch.long).unsqueeze(1)).repeat(1, nseg)  # [S, nseg*R]
+    for slot in torch.unique(adapter_ids).tolist():
+        if slot < 0:
+            continue
+        rows = adapter_ids == slot
+        t[rows] = (x[rows].float() @ A[slot].float().T) * live[slot].float()
+    return t
+
+
+def lora_expand(
+    y: torch.Tensor, t: torch.Tensor, B: torch.Tensor, ranks: torch.Tensor,
+    scales: torch.Tensor, adapter_ids: torch.Tensor, seg_bounds,
+) -> torch.Tensor:
+    """In place: y[row, n] = (float(y[row, n]) + scale[slot] * sum_j
+    t[row, seg(n)*R + j] * B[slot, n, j]) rounded to y's dtype; rows of
+    slot -1 are not touched."""
+    R = B.shape[2]
+    for slot in torch.unique(adapter_ids).tolist():
+        if slot < 0:
+            continue
+        rows = adapter_ids == slot
+        r = int(ranks[slot])
+        tr = t[rows]
+        yr = y[rows].float()
+        lo = 0
+        for s, hi in enumerate(seg_bounds):
+            yr[:, lo:hi] += float(scales[slot]) * (
+                tr[:, s * R : s * R + r] @ B[slot, lo:hi, :r].float().T
+            )
+            lo = hi
+        y[rows] = yr.to(y.dtype)
+    return y
+
+
 FP8_MAX = 448.0  # e4m3fn
 
 

@@ -29,6 +29,7 @@ sources = [
     os.path.join(CSRC, "gemm_w8_m256.hip"),
     os.path.join(CSRC, "gemm_w4.hip"),
     os.path.join(CSRC, "gemm_w4_m256.hip"),
+    os.path.join(CSRC, "lora.hip"),
 ]
 
 setup(
