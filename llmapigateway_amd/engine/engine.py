@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..models.configs import ModelConfig, get_model_config
+from ..models.configs import ModelConfig, check_moe_supported, get_model_config
 from ..models.llama import ForwardBatch, LlamaModel
 from .kvcache import PagedKVCache
 
@@ -189,6 +189,8 @@ class LLMEngine:
                 "parallelism (tp_size > 1) yet"
             )
         full_config = get_model_config(model) if isinstance(model, str) else model
+        # mixture of experts: say early what it cannot be combined with yet
+        check_moe_supported(full_config, tp_size, max_loras=max_loras)
         if sliding_window is not None:
             # overrides the preset's window; 0 turns it off
             if sliding_window < 0:
@@ -223,6 +225,7 @@ class LLMEngine:
         if weight_dtype == "auto":
             weight_dtype = os.environ.get("LLMAPI_WEIGHT_DTYPE", "auto")
         self.weight_dtype = weight_dtype  # "auto" (= compute dtype) | "fp8" | "mxfp4"
+        check_moe_supported(full_config, tp_size, weight_dtype, max_loras)
         self.model = LlamaModel(
             config, device=self.device, dtype=dtype, seed=seed,
             tp_group=tp_group, tp_rank=tp_rank, tp_size=tp_size,

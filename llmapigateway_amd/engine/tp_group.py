@@ -247,10 +247,11 @@ class TPEngineClient:
         start_timeout: float = 600.0,
         weight_dtype: str = "auto",
     ):
-        from ..models.configs import get_model_config
+        from ..models.configs import check_moe_supported, get_model_config
         from .tokenizer import get_tokenizer
 
         self.full_config = get_model_config(model) if isinstance(model, str) else model
+        check_moe_supported(self.full_config, tp, weight_dtype)  # before any worker starts
         self.tokenizer = get_tokenizer("auto", self.full_config.vocab_size)
         self.max_model_len = max_model_len or self.full_config.max_positions
         self.tp = tp

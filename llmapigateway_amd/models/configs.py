@@ -27,6 +27,10 @@ class ModelConfig:
     # sliding-window attention: a token attends to the last W positions
     # (itself included); None = full causal attention
     sliding_window: Optional[int] = None
+    # mixture of experts (Mixtral-style): num_experts expert MLPs per layer,
+    # experts_per_token of them chosen per token; 0 = a dense model
+    num_experts: int = 0
+    experts_per_token: int = 0
 
     @property
     def q_size(self) -> int:
@@ -115,6 +119,20 @@ MODEL_PRESETS = {
         max_positions=32768,
         sliding_window=4096,
     ),
+    # Mixtral-8x7B: Mistral's attention (no window), 8 expert MLPs, top-2
+    "mixtral-8x7b": ModelConfig(
+        name="mixtral-8x7b",
+        hidden_size=4096,
+        intermediate_size=14336,
+        num_layers=32,
+        num_heads=32,
+        num_kv_heads=8,
+        vocab_size=32000,
+        rope_theta=1000000.0,
+        max_positions=32768,
+        num_experts=8,
+        experts_per_token=2,
+    ),
     # tiny shapes for CPU tests / smoke
     "tiny-llama": ModelConfig(
         name="tiny-llama",
@@ -127,6 +145,21 @@ MODEL_PRESETS = {
         head_dim=64,
         rope_theta=10000.0,
         max_positions=512,
+    ),
+    # tiny-llama with 4 experts, top-2 (mixture-of-experts tests)
+    "tiny-mixtral": ModelConfig(
+        name="tiny-mixtral",
+        hidden_size=256,
+        intermediate_size=512,
+        num_layers=2,
+        num_heads=4,
+        num_kv_heads=2,
+        vocab_size=512,
+        head_dim=64,
+        rope_theta=10000.0,
+        max_positions=512,
+        num_experts=4,
+        experts_per_token=2,
     ),
     # tiny-llama with a sliding window (window and block-release tests)
     "tiny-llama-swa": ModelConfig(
@@ -168,6 +201,31 @@ MODEL_PRESETS = {
         rope_theta=500000.0,
     ),
 }
+
+
+def check_moe_supported(
+    config: ModelConfig, tp_size: int = 1, weight_dtype: str = "auto",
+    max_loras: int = 0,
+) -> None:
+    """What a mixture-of-experts config cannot be combined with yet; each is
+    its own follow-up (docs/ROADMAP.md). A dense config passes."""
+    if not config.num_experts:
+        return
+    if tp_size > 1:
+        raise NotImplementedError(
+            "mixture-of-experts models (num_experts > 0) are not supported "
+            "with tensor parallelism (tp_size > 1) yet"
+        )
+    if weight_dtype != "auto":
+        raise NotImplementedError(
+            "mixture-of-experts models (num_experts > 0) are not supported "
+            f"with quantised weights (weight_dtype={weight_dtype!r}) yet"
+        )
+    if max_loras > 0:
+        raise NotImplementedError(
+            "mixture-of-experts models (num_experts > 0) are not supported "
+            "with LoRA adapters (max_loras > 0) yet"
+        )
 
 
 def get_model_config(name: str) -> ModelConfig:

@@ -27,6 +27,12 @@ per-row delta after each projection GEMM (ops.lora_add, ops/csrc/lora.hip);
 o/down then run linear + delta + rmsnorm_residual and gate_up linear + delta
 + swiglu, not the fused ops (see forward()).
 
+Mixture of experts: a config with ``num_experts > 0`` (Mixtral) holds a
+router and two expert stacks per layer in place of gate_up/down, and the MLP
+tail of every layer is one ops.moe_mlp call (ops/csrc/moe.hip: routing, a
+counting sort of the (token, choice) pairs by expert, two grouped MFMA GEMMs
+and the combine + norm). Attention, qkv and o are the dense model's.
+
 Tensor parallelism: construct with ``tp_group`` + a config pre-sharded via
 ModelConfig.scaled_for_tp; qkv/gate_up are column-sharded, o/down
 row-sharded with an RCCL all-reduce over xGMI after each (2 per layer).
@@ -43,7 +49,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from .. import ops
-from .configs import ModelConfig
+from .configs import ModelConfig, check_moe_supported
 
 
 @dataclass
@@ -103,6 +109,13 @@ class LlamaModel:
         # "mxfp4": the same four as OCP MXFP4 — e2m1 nibbles plus one e8m0
         # scale per 32 k of a row (fragment-major,
         # ops.swizzle_weight_frag_mxfp4) — run through ops.linear_w4
+        # mixture of experts: not with TP, quantised weights or adapters yet
+        check_moe_supported(config, tp_size, weight_dtype, max_loras)
+        if config.num_experts:
+            ops.moe_check_shapes(
+                config.num_experts, config.experts_per_token,
+                config.hidden_size, config.intermediate_size,
+            )
         self.weight_dtype = weight_dtype
         self.config = config
         self.full_config = full_config or config
@@ -141,9 +154,13 @@ class LlamaModel:
         hidden = c.hidden_size
         # tiny models init on CPU (deterministic across devices, for tests);
         # big models init directly on the GPU (CPU RNG would take minutes at 8B+)
+        n_mlp = max(c.num_experts, 1)  # expert MLPs per layer (+ the router)
         approx_params = (
             2 * self.full_config.vocab_size * hidden
-            + c.num_layers * hidden * (c.q_size + 2 * c.kv_size + c.q_size + 3 * c.intermediate_size) // 1
+            + c.num_layers * hidden * (
+                c.q_size + 2 * c.kv_size + c.q_size
+                + n_mlp * 3 * c.intermediate_size + c.num_experts
+            )
         )
         init_device = torch.device("cpu") if approx_params < 10**8 else self.device
         gen = torch.Generator(device=init_device).manual_seed(seed)
@@ -168,6 +185,9 @@ class LlamaModel:
         for _ in range(c.num_layers):
             qkv_full = mk(fc.q_size + 2 * fc.kv_size, hidden, std)
             o_full = mk(hidden, fc.q_size, out_std)
+            if c.num_experts:
+                self.layers.append(self._moe_layer(qkv_full, o_full, mk, std, out_std))
+                continue
             gu_full = mk(2 * fc.intermediate_size, hidden, std)
             down_full = mk(hidden, fc.intermediate_size, out_std)
             if quant:
@@ -199,7 +219,39 @@ class LlamaModel:
         if quant:
             self._reserve_w8_buffer()
             return  # no bf16 matrices, so no bf16 twins
+        if c.num_experts and self.device.type == "cuda":
+            # hand the packing temporaries back: the KV pool is sized from
+            # free memory
+            torch.cuda.empty_cache()
         self._build_twins()
+
+    def _moe_layer(self, qkv, o, mk, std: float, out_std: float) -> Dict[str, torch.Tensor]:
+        """One layer of a mixture-of-experts config: the router [E, H] and
+        the expert stacks in place of gate_up/down, drawn in a fixed order
+        (router, every expert's gate_up, every expert's down). On the GPU
+        the stacks are held packed only (ops.moe_pack_weights: ONE resident
+        copy, no twins); on the CPU they stay plain [E, 2I, H] / [E, H, I]."""
+        c = self.config
+        E, hidden, inter = c.num_experts, c.hidden_size, c.intermediate_size
+        router = mk(E, hidden, std)
+        gate_up = torch.empty(E, 2 * inter, hidden, dtype=self.dtype, device=self.device)
+        for e in range(E):
+            gate_up[e] = mk(2 * inter, hidden, std)
+        down = torch.empty(E, hidden, inter, dtype=self.dtype, device=self.device)
+        for e in range(E):
+            down[e] = mk(hidden, inter, out_std)
+        if self.device.type == "cuda":
+            gate_up = ops.moe_pack_weights(gate_up, True)
+            down = ops.moe_pack_weights(down, False)
+        return {
+            "input_norm": torch.ones(hidden, dtype=self.dtype, device=self.device),
+            "qkv": qkv,
+            "o": o,
+            "post_norm": torch.ones(hidden, dtype=self.dtype, device=self.device),
+            "router": router,
+            "experts_gate_up": gate_up,
+            "experts_down": down,
+        }
 
     def _quant_layer(self, qkv_full, o_full, gu_full, down_full) -> Dict[str, torch.Tensor]:
         """One layer's dict in a quantised mode, from the full (unsharded)
@@ -285,6 +337,7 @@ class LlamaModel:
         an oracle and an accuracy A/B."""
         if mode not in ("fp8", "mxfp4"):
             raise ValueError(f"unknown quantisation mode {mode!r}")
+        check_moe_supported(self.config, weight_dtype=mode)
         if self.weight_dtype != "auto":
             raise RuntimeError(f"weights are already {self.weight_dtype}")
         if self.tp_size > 1:
@@ -334,6 +387,8 @@ class LlamaModel:
             legacy = bool(_os.environ.get("LLMAPI_SWZ_WEIGHTS"))
             for layer in self.layers:
                 for name in ("qkv", "o", "gate_up", "down"):
+                    if name not in layer:  # expert stacks have no twins
+                        continue
                     w = layer[name]
                     if legacy:
                         if w.shape[0] % 64 == 0 and w.shape[1] % 32 == 0:
@@ -358,9 +413,10 @@ class LlamaModel:
                         )
                     ):
                         layer[name + "_swz"] = ops.swizzle_weight_frag(w)
-                gu = layer["gate_up"]
+                gu = layer.get("gate_up")
                 if (
-                    not legacy
+                    gu is not None
+                    and not legacy
                     # with adapters resident gate_up never takes the fused
                     # swiglu route (forward()): its twin would be dead HBM
                     and not getattr(self, "max_loras", 0)
@@ -687,6 +743,13 @@ class LlamaModel:
                 attn.reshape(T, c.q_size), layer, "o",
                 residual, layer["post_norm"],
             )
+            if c.num_experts:
+                x, residual = ops.moe_mlp(
+                    x, layer["router"], layer["experts_gate_up"],
+                    layer["experts_down"], c.experts_per_token, residual,
+                    next_norm, c.rms_eps,
+                )
+                continue
             if self.weight_dtype != "auto":
                 act = ops.swiglu(self._linear(x, layer, "gate_up"))
             else:

@@ -54,6 +54,7 @@ from .reference import (  # re-export (MXFP4 weight quantisation scheme)
     swizzle_weight_frag_mxfp4,
     unswizzle_weight_frag_mxfp4,
 )
+from .reference import moe_unpack_weights  # re-export (inverse of moe_pack_weights)
 
 _C = None
 _C_ERR: Optional[str] = None
@@ -1247,6 +1248,163 @@ def lora_add(
     )
 
 
+# ---- mixture of experts: routing + grouped expert MLP (csrc/moe.hip) ----
+# CPU tensors take the plain-loop reference with plain expert weights
+# ([E, 2I, H] / [E, H, I]). GPU tensors take the HIP kernels with PACKED
+# expert weights (moe_pack_weights) and a MoePlan from moe_align; there the
+# act between the two GEMMs is [cap, I] in the plan's sorted order, not
+# [T*k, I] in pair order.
+MOE_MAX_EXPERTS = 64  # keep in sync with MOE_MAX_E / MOE_MAX_K in moe.hip
+MOE_MAX_TOPK = 8
+MOE_MAX_HIDDEN = 8192  # moe_route: four x rows in 64 KiB of dynamic LDS
+
+
+def moe_check_shapes(E: int, k: int, H: int, inter: int) -> None:
+    """The shapes the MoE kernels serve; anything else is an error."""
+    if not (2 <= E <= MOE_MAX_EXPERTS):
+        raise ValueError(f"MoE needs 2 <= num_experts <= {MOE_MAX_EXPERTS}, got {E}")
+    if not (1 <= k <= min(E, MOE_MAX_TOPK)):
+        raise ValueError(
+            f"MoE needs 1 <= experts_per_token <= min(num_experts, "
+            f"{MOE_MAX_TOPK}), got {k} of {E}"
+        )
+    if H % 64 or inter % 64:
+        raise ValueError(
+            f"MoE needs hidden and intermediate sizes in multiples of 64, "
+            f"got {H} and {inter}"
+        )
+    if H > MOE_MAX_HIDDEN:
+        raise ValueError(
+            f"MoE needs hidden size <= {MOE_MAX_HIDDEN} (the router holds four "
+            f"x rows in 64 KiB of LDS), got {H}"
+        )
+
+
+class MoePlan:
+    """moe_align's result. sorted_pairs [cap] int32: pair index t*k + j, every
+    expert's pairs together and padded with -1 to a multiple of BM = 16*mf;
+    tile_expert [cap / BM] int32: expert of a row tile, -1 = unused."""
+
+    def __init__(self, sorted_pairs, tile_expert, mf: int):
+        self.sorted_pairs, self.tile_expert, self.mf = sorted_pairs, tile_expert, mf
+        self.cap = sorted_pairs.numel()
+
+
+def moe_pack_weights(w: torch.Tensor, gate_up: bool) -> torch.Tensor:
+    """[E, N, K] expert stack -> the resident GPU layout (on w's device)."""
+    return reference.moe_pack_weights(w, gate_up)
+
+
+def moe_cap(P: int, E: int, mf: int) -> int:
+    """Rows of the sorted order for P pairs in the worst case: every expert
+    may pad up to BM - 1 rows; rounded up to whole tiles."""
+    bm = 16 * mf
+    return -(-(P + E * (bm - 1)) // bm) * bm
+
+
+def moe_route(x: torch.Tensor, w_router: torch.Tensor, k: int):
+    """-> (ids [T, k] int32, weights [T, k] fp32), reference.moe_route."""
+    if not x.is_cuda:
+        return reference.moe_route(x, w_router, k)
+    T = x.shape[0]
+    ids = torch.empty(T, k, dtype=torch.int32, device=x.device)
+    weights = torch.empty(T, k, dtype=torch.float32, device=x.device)
+    _native().moe_route(ids, weights, x, w_router)
+    return ids, weights
+
+
+def moe_align(ids: torch.Tensor, E: int, mf: Optional[int] = None) -> MoePlan:
+    """GPU only: sort the pairs of ids [T, k] by expert. mf (1, 2, 4) is the
+    row-tile factor; by default picked from the host integers T*k/E."""
+    T, k = ids.shape
+    if mf is None:
+        mf = _native().moe_pick_mf(T, k, E)
+    cap = moe_cap(T * k, E, mf)
+    sorted_pairs = torch.empty(cap, dtype=torch.int32, device=ids.device)
+    tile_expert = torch.empty(cap // (16 * mf), dtype=torch.int32, device=ids.device)
+    _native().moe_align(sorted_pairs, tile_expert, ids, E, mf)
+    return MoePlan(sorted_pairs, tile_expert, mf)
+
+
+def moe_gate_up_swiglu(
+    x: torch.Tensor, ids: torch.Tensor, w_gate_up: torch.Tensor,
+    plan: Optional[MoePlan] = None, out: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """swiglu(x[t] @ w_gate_up[ids[t, j]].T) per pair. CPU: [T*k, I] in pair
+    order. GPU: w_gate_up packed, act [plan.cap, I] in sorted order (padding
+    rows are not written), into `out` when given."""
+    if not x.is_cuda:
+        return reference.moe_gate_up_swiglu(x, ids, w_gate_up)
+    if plan is None:
+        raise ValueError("moe_gate_up_swiglu on the GPU needs moe_align's plan")
+    k = ids.shape[1]
+    inter = w_gate_up.shape[2] * 8
+    act = out
+    if act is None:
+        act = torch.empty(plan.cap, inter, dtype=x.dtype, device=x.device)
+    _native().moe_gemm(act, x, w_gate_up, plan.sorted_pairs, plan.tile_expert,
+                       None, 0, plan.mf, k, ids.numel())
+    return act
+
+
+def moe_down(
+    act: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor,
+    w_down: torch.Tensor, plan: Optional[MoePlan] = None,
+    out: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """y_pair [T*k, H] = weights[t, j] * (act row @ w_down[ids[t, j]].T) in
+    pair order. GPU: act in the plan's sorted order, w_down packed; into
+    `out` when given."""
+    if not act.is_cuda:
+        return reference.moe_down(act, ids, weights, w_down)
+    if plan is None:
+        raise ValueError("moe_down on the GPU needs moe_align's plan")
+    y_pair = out
+    if y_pair is None:
+        y_pair = torch.empty(ids.numel(), w_down.shape[2] * 16, dtype=act.dtype,
+                             device=act.device)
+    _native().moe_gemm(y_pair, act, w_down, plan.sorted_pairs, plan.tile_expert,
+                       weights, 1, plan.mf, ids.shape[1], ids.numel())
+    return y_pair
+
+
+def moe_combine_rmsnorm_residual(
+    y_pair: torch.Tensor, residual: torch.Tensor, norm_w: torch.Tensor,
+    eps: float, k: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Sum a token's k rows of y_pair in fixed order, add the residual (in
+    place on the GPU) and norm -> (normed, residual)."""
+    if not y_pair.is_cuda:
+        return reference.moe_combine_rmsnorm_residual(y_pair, residual, norm_w, eps, k)
+    normed = torch.empty_like(residual)
+    _native().moe_combine_norm(normed, residual, y_pair, norm_w, eps, k)
+    return normed, residual
+
+
+def moe_mlp(
+    x: torch.Tensor, w_router: torch.Tensor, w_gate_up: torch.Tensor,
+    w_down: torch.Tensor, k: int, residual: torch.Tensor,
+    norm_w: torch.Tensor, eps: float = 1e-5,
+    ids: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The MoE layer tail -> (normed, residual): five launches on the GPU
+    (route, align, gate_up+swiglu, down, combine+norm), none of which reads
+    device data on the host. ids/weights given: the router is skipped."""
+    if not x.is_cuda:
+        if ids is None:
+            return reference.moe_mlp(x, w_router, w_gate_up, w_down, k, residual,
+                                     norm_w, eps)
+        act = reference.moe_gate_up_swiglu(x, ids, w_gate_up)
+        y_pair = reference.moe_down(act, ids, weights, w_down)
+        return reference.moe_combine_rmsnorm_residual(y_pair, residual, norm_w, eps, k)
+    if ids is None:
+        ids, weights = moe_route(x, w_router, k)
+    plan = moe_align(ids, w_gate_up.shape[0])
+    act = moe_gate_up_swiglu(x, ids, w_gate_up, plan)
+    y_pair = moe_down(act, ids, weights, w_down, plan)
+    return moe_combine_rmsnorm_residual(y_pair, residual, norm_w, eps, k)
+
+
 def topk_topp_filter(
     logits: torch.Tensor, topp: torch.Tensor, topk: torch.Tensor
 ) -> torch.Tensor:
@@ -1311,6 +1469,17 @@ __all__ = [
     "lora_shrink",
     "lora_expand",
     "lora_add",
+    "MoePlan",
+    "moe_check_shapes",
+    "moe_pack_weights",
+    "moe_unpack_weights",
+    "moe_cap",
+    "moe_route",
+    "moe_align",
+    "moe_gate_up_swiglu",
+    "moe_down",
+    "moe_combine_rmsnorm_residual",
+    "moe_mlp",
     "attention_prefill",
     "attention_decode",
     "sample",

@@ -25,6 +25,11 @@ hipError_t launch_sample(int64_t*, const float*, const float*, const float*, flo
 hipError_t launch_topk_topp_filter(float*, const float*, const int*, int, int, hipStream_t);
 hipError_t launch_lora_shrink(float*, const void*, const void*, const int*, const int*, int, int, int, int, int, hipStream_t);
 hipError_t launch_lora_expand(void*, const float*, const void*, const int*, const float*, const int*, int, int, int, int, int, int, int, hipStream_t);
+int moe_pick_mf(int, int, int);
+hipError_t launch_moe_route(int*, float*, const void*, const void*, int, int, int, int, hipStream_t);
+hipError_t launch_moe_align(int*, int*, const int*, int, int, int, int, hipStream_t);
+hipError_t launch_moe_gemm(void*, const void*, const void*, const int*, const int*, const float*, int, int, int, int, int, int, hipStream_t);
+hipError_t launch_moe_combine_norm(void*, void*, const void*, const void*, float, int, int, int, hipStream_t);
 }
 
 namespace {
@@ -624,9 +629,140 @@ void lora_expand(torch::Tensor y, torch::Tensor t, torch::Tensor B,
                                  current_stream()));
 }
 
+// ---- mixture of experts (moe.hip) ----
+void check_moe_shape(int64_t E, int64_t k) {
+    TORCH_CHECK(E >= 2 && E <= 64, "MoE kernels support 2 <= num_experts <= 64, got ", E);
+    TORCH_CHECK(k >= 1 && k <= 8 && k <= E,
+                "MoE kernels support 1 <= experts_per_token <= min(num_experts, 8), got ", k);
+}
+
+void check_i32(const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt32 && t.is_contiguous(),
+                name, " must be a contiguous int32 GPU tensor");
+}
+
+int64_t moe_pick_mf_py(int64_t T, int64_t k, int64_t E) {
+    return moe_pick_mf((int)T, (int)k, (int)E);
+}
+
+void moe_route(torch::Tensor ids, torch::Tensor weights, torch::Tensor x,
+               torch::Tensor w_router) {
+    check_bf16(x, "x");
+    check_bf16(w_router, "w_router");
+    TORCH_CHECK(x.dim() == 2 && w_router.dim() == 2 && x.is_contiguous() &&
+                w_router.is_contiguous() && w_router.size(1) == x.size(1),
+                "x [T, H] and w_router [E, H] must be contiguous");
+    const int64_t T = x.size(0), H = x.size(1), E = w_router.size(0);
+    check_i32(ids, "ids");
+    TORCH_CHECK(ids.dim() == 2 && ids.size(0) == T, "ids must be int32 [T, k]");
+    const int64_t k = ids.size(1);
+    check_moe_shape(E, k);
+    TORCH_CHECK(H % 64 == 0 && H <= 8192, "moe_route needs H % 64 == 0 and H <= 8192, got ", H);
+    TORCH_CHECK(weights.is_cuda() && weights.scalar_type() == torch::kFloat32 &&
+                weights.is_contiguous() && weights.sizes() == ids.sizes(),
+                "weights must be fp32 [T, k]");
+    CHECK_HIP(launch_moe_route(ids.data_ptr<int>(), weights.data_ptr<float>(),
+                               x.data_ptr(), w_router.data_ptr(), (int)T, (int)H,
+                               (int)E, (int)k, current_stream()));
+}
+
+void moe_align(torch::Tensor sorted_pairs, torch::Tensor tile_expert,
+               torch::Tensor ids, int64_t E, int64_t mf) {
+    check_i32(sorted_pairs, "sorted_pairs");
+    check_i32(tile_expert, "tile_expert");
+    check_i32(ids, "ids");
+    TORCH_CHECK(mf == 1 || mf == 2 || mf == 4, "mf must be 1, 2 or 4");
+    TORCH_CHECK(E >= 2 && E <= 64, "MoE kernels support 2 <= num_experts <= 64, got ", E);
+    const int64_t P = ids.numel(), BM = 16 * mf, tiles = tile_expert.numel();
+    TORCH_CHECK(P > 0 && tiles * BM >= P + E * (BM - 1) &&
+                sorted_pairs.numel() == tiles * BM,
+                "sorted_pairs [cap] / tile_expert [cap / BM] too small for ", P,
+                " pairs of ", E, " experts");
+    CHECK_HIP(launch_moe_align(sorted_pairs.data_ptr<int>(),
+                               tile_expert.data_ptr<int>(), ids.data_ptr<int>(),
+                               (int)P, (int)E, (int)mf, (int)tiles,
+                               current_stream()));
+}
+
+// epi 0: out = act [cap, I], a = x [T, H], w packed [E, H/32, 2I/16, 64, 8]
+// epi 1: out = y_pair [P, H], a = act [cap, I], w packed [E, I/32, H/16, 64, 8]
+void moe_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w,
+              torch::Tensor sorted_pairs, torch::Tensor tile_expert,
+              c10::optional<torch::Tensor> rweights, int64_t epi, int64_t mf,
+              int64_t k, int64_t P) {
+    check_bf16(out, "out");
+    check_bf16(a, "a");
+    check_bf16(w, "w");
+    check_i32(sorted_pairs, "sorted_pairs");
+    check_i32(tile_expert, "tile_expert");
+    TORCH_CHECK(epi == 0 || epi == 1, "epi must be 0 (swiglu) or 1 (down)");
+    TORCH_CHECK(mf == 1 || mf == 2 || mf == 4, "mf must be 1, 2 or 4");
+    TORCH_CHECK(out.is_contiguous() && a.is_contiguous() && w.is_contiguous() &&
+                out.dim() == 2 && a.dim() == 2);
+    TORCH_CHECK(w.dim() == 5 && w.size(3) == 64 && w.size(4) == 8,
+                "w must be packed [E, K/32, N/16, 64, 8] (ops.moe_pack_weights)");
+    const int64_t E = w.size(0), K = w.size(1) * 32, N = w.size(2) * 16;
+    const int64_t BM = 16 * mf, tiles = tile_expert.numel(), cap = tiles * BM;
+    check_moe_shape(E, k);
+    TORCH_CHECK(sorted_pairs.numel() == cap, "sorted_pairs must be [cap]");
+    TORCH_CHECK(K % 64 == 0 && a.size(1) == K, "a must be [rows, K] with K % 64 == 0");
+    // P = T * k pairs; only the down epilogue reads the routing weights
+    const float* rw = nullptr;
+    if (epi == 1) {
+        TORCH_CHECK(rweights.has_value() && rweights->is_cuda() &&
+                    rweights->scalar_type() == torch::kFloat32 &&
+                    rweights->is_contiguous() && rweights->numel() == P,
+                    "weights must be fp32 [T, k]");
+        rw = rweights->data_ptr<float>();
+    }
+    TORCH_CHECK(P > 0 && P % k == 0 && cap >= P + E * (BM - 1),
+                "cap too small for the pairs");
+    if (epi == 0) {
+        TORCH_CHECK(N % 128 == 0, "intermediate size must be a multiple of 64");
+        TORCH_CHECK(a.size(0) == P / k, "x must be [T, H]");
+        TORCH_CHECK(out.size(0) == cap && out.size(1) == N / 2, "act must be [cap, I]");
+    } else {
+        TORCH_CHECK(N % 64 == 0, "hidden size must be a multiple of 64");
+        TORCH_CHECK(a.size(0) == cap, "act must be [cap, I]");
+        TORCH_CHECK(out.size(0) == P && out.size(1) == N, "y_pair must be [T*k, H]");
+    }
+    CHECK_HIP(launch_moe_gemm(out.data_ptr(), a.data_ptr(), w.data_ptr(),
+                              sorted_pairs.data_ptr<int>(),
+                              tile_expert.data_ptr<int>(),
+                              rw, (int)epi, (int)mf,
+                              (int)tiles, (int)N, (int)K, (int)k,
+                              current_stream()));
+}
+
+void moe_combine_norm(torch::Tensor normed, torch::Tensor residual,
+                      torch::Tensor y_pair, torch::Tensor norm_w, double eps,
+                      int64_t k) {
+    check_bf16(normed, "normed");
+    check_bf16(residual, "residual");
+    check_bf16(y_pair, "y_pair");
+    check_bf16(norm_w, "norm_w");
+    TORCH_CHECK(normed.is_contiguous() && residual.is_contiguous() &&
+                y_pair.is_contiguous() && norm_w.is_contiguous());
+    TORCH_CHECK(residual.dim() == 2 && k >= 1 && k <= 8);
+    const int64_t T = residual.size(0), H = residual.size(1);
+    TORCH_CHECK(H % 8 == 0 && y_pair.numel() == T * k * H &&
+                normed.numel() == T * H && norm_w.numel() == H,
+                "moe_combine_norm: y_pair [T*k, H], residual/normed [T, H]");
+    CHECK_HIP(launch_moe_combine_norm(normed.data_ptr(), residual.data_ptr(),
+                                      y_pair.data_ptr(), norm_w.data_ptr(),
+                                      (float)eps, (int)T, (int)H, (int)k,
+                                      current_stream()));
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    m.def("moe_pick_mf", &moe_pick_mf_py, "row-tile factor (BM = 16 mf) for T, k, E");
+    m.def("moe_route", &moe_route, "MoE router: softmax top-k ids and weights per row");
+    m.def("moe_align", &moe_align, "MoE counting sort of the pairs by expert, BM-padded");
+    m.def("moe_gemm", &moe_gemm, "grouped expert GEMM (epi 0: gate_up+swiglu, 1: down)");
+    m.def("moe_combine_norm", &moe_combine_norm,
+          "sum of a token's k expert rows + residual add + RMSNorm");
     m.def("lora_shrink", &lora_shrink,
           "batched-gather LoRA shrink t = x @ A[slot].T (fp32), slot per row");
     m.def("lora_expand", &lora_expand,

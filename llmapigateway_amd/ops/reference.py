@@ -134,6 +134,119 @@ def lora_expand(
     return y
 
 
+# ---- mixture of experts (Mixtral-style): E expert MLPs, k per token ----
+# Pair (t, j) is the j-th choice of token t, flat index t*k + j. Expert
+# weights here are plain: w_gate_up [E, 2I, H] ([gate; up] stacked like the
+# dense gate_up) and w_down [E, H, I]. Plain loops over experts.
+
+def moe_route(x: torch.Tensor, w_router: torch.Tensor, k: int):
+    """(ids [T, k] int32, weights [T, k] fp32): fp32 router logits, softmax
+    over all E, the k largest in descending weight with a tie going to the
+    LOWER expert index (a stable sort says so explicitly), renormalised to
+    sum to 1 (Mixtral's rule)."""
+    probs = torch.softmax(x.float() @ w_router.float().T, dim=-1)
+    order = torch.sort(probs, dim=-1, descending=True, stable=True).indices[:, :k]
+    top = torch.gather(probs, 1, order)
+    return order.to(torch.int32), top / top.sum(dim=-1, keepdim=True)
+
+
+def moe_gate_up_swiglu(
+    x: torch.Tensor, ids: torch.Tensor, w_gate_up: torch.Tensor
+) -> torch.Tensor:
+    """act [T*k, I]: act[t*k + j] = swiglu(x[t] @ w_gate_up[ids[t, j]].T),
+    the swiglu on the fp32 products, one rounding to x's dtype."""
+    T, k = ids.shape
+    inter = w_gate_up.shape[1] // 2
+    flat = ids.reshape(-1).long()
+    xp = x.float().repeat_interleave(k, dim=0)  # row of every pair
+    act = torch.zeros(T * k, inter, dtype=torch.float32, device=x.device)
+    for e in torch.unique(flat).tolist():
+        rows = flat == e
+        h = xp[rows] @ w_gate_up[e].float().T
+        g, u = h[:, :inter], h[:, inter:]
+        act[rows] = g * torch.sigmoid(g) * u
+    return act.to(x.dtype)
+
+
+def moe_down(
+    act: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor,
+    w_down: torch.Tensor,
+) -> torch.Tensor:
+    """y_pair [T*k, H]: weights[t, j] * (act[t*k + j] @ w_down[ids[t, j]].T),
+    the weight applied in fp32 before the single rounding."""
+    flat = ids.reshape(-1).long()
+    y = torch.zeros(act.shape[0], w_down.shape[1], dtype=torch.float32,
+                    device=act.device)
+    for e in torch.unique(flat).tolist():
+        rows = flat == e
+        y[rows] = act[rows].float() @ w_down[e].float().T
+    return (weights.reshape(-1, 1).float() * y).to(act.dtype)
+
+
+def moe_combine_rmsnorm_residual(
+    y_pair: torch.Tensor, residual: torch.Tensor, norm_w: torch.Tensor,
+    eps: float, k: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 sum over j = 0..k-1 (in that order) of y_pair[t*k + j], plus
+    residual[t], rounded once as the new residual; then its rmsnorm. k = 1
+    is rmsnorm_residual."""
+    T, H = residual.shape
+    yp = y_pair.float().view(T, k, H)
+    s = yp[:, 0]
+    for j in range(1, k):
+        s = s + yp[:, j]
+    r = (s + residual.float()).to(residual.dtype)
+    return rmsnorm(r, norm_w, eps), r
+
+
+def moe_mlp(
+    x: torch.Tensor, w_router: torch.Tensor, w_gate_up: torch.Tensor,
+    w_down: torch.Tensor, k: int, residual: torch.Tensor,
+    norm_w: torch.Tensor, eps: float = 1e-5,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The MoE layer tail: route, expert MLPs, combine + residual + norm ->
+    (normed, residual)."""
+    ids, weights = moe_route(x, w_router, k)
+    act = moe_gate_up_swiglu(x, ids, w_gate_up)
+    y_pair = moe_down(act, ids, weights, w_down)
+    return moe_combine_rmsnorm_residual(y_pair, residual, norm_w, eps, k)
+
+
+def moe_pack_weights(w: torch.Tensor, gate_up: bool) -> torch.Tensor:
+    """Expert stack [E, N, K] -> the one resident GPU layout, fragment-major
+    per expert [E, K/32, N/16, 64, 8]: element [e][k32][n16][lane][i] =
+    W[e][n16*16 + (lane & 15)][k32*32 + (lane >> 4)*8 + i], one wave's
+    mfma_f32_16x16x32_bf16 B fragment per KiB. gate_up=True first permutes
+    the rows of [gate; up] to block-16 interleaved order (g0..15, u0..15,
+    g16..31, ...), so the gate and up accumulators of an output column meet
+    in one lane of adjacent fragments."""
+    E, N, K = w.shape
+    if N % 64 or K % 64:
+        raise ValueError(f"expert weights need N, K in multiples of 64, got {(N, K)}")
+    if gate_up:
+        w = w.view(E, 2, N // 32, 16, K).transpose(1, 2).reshape(E, N, K)
+    return (
+        w.view(E, N // 16, 16, K // 32, 4, 8)
+        .permute(0, 3, 1, 4, 2, 5)
+        .reshape(E, K // 32, N // 16, 64, 8)
+        .contiguous()
+    )
+
+
+def moe_unpack_weights(p: torch.Tensor, gate_up: bool) -> torch.Tensor:
+    """Inverse of moe_pack_weights: -> [E, N, K]."""
+    E, k32, n16 = p.shape[:3]
+    N, K = n16 * 16, k32 * 32
+    w = (
+        p.view(E, k32, n16, 4, 16, 8)
+        .permute(0, 2, 4, 1, 3, 5)
+        .reshape(E, N, K)
+    )
+    if gate_up:
+        w = w.view(E, N // 32, 2, 16, K).transpose(1, 2).reshape(E, N, K)
+    return w.contiguous()
+
+
 FP8_MAX = 448.0  # e4m3fn
 
 

@@ -1,0 +1,157 @@
+"""Cold-cache timing of the mixture-of-experts MLP (ops.moe_mlp,
+csrc/moe.hip) on Mixtral-8x7B's shapes (H 4096, I 14336, 8 experts, top-2)
+with uniform-random routing, beside two baselines at the same T:
+
+  (a) the dense llama-3-8b MLP on the existing route (ops.swiglu_linear +
+      ops.linear_rmsnorm_residual): one expert's worth of weights, the floor
+      a k-of-E layer cannot reach;
+  (b) a per-expert loop of library GEMMs on rows PRE-SORTED by expert
+      (the sort and the gather are done once, outside the timed call). Timed
+      are the read-back of the per-expert row counts, the two library GEMMs
+      and the swiglu per expert, and one weighted combine + norm. THE HOST
+      SYNCS once per call on the counts, so the route cannot be captured
+      into a decode graph.
+
+The last column times moe_align alone (warm, the sort of the T*k pairs).
+
+As in tools/lora_bench.py every route cycles through several layers' worth of
+weights (each layer's experts are 2.8 GB, far beyond the 256 MB L3), routes
+alternate, three rounds each; the median round is reported with the min-max
+of the three. Run on the GPU box:
+
+    python tools/moe_bench.py [--ts=16,64,256,4096]
+"""
+
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch
+
+from llmapigateway_amd import ops
+
+H, INTER, E, K = 4096, 14336, 8, 2
+TS = (16, 64, 256, 4096)
+MOE_LAYERS = 2    # 5.6 GB of expert weights per form
+DENSE_LAYERS = 5  # 1.7 GB of dense MLP weights
+
+
+def timed(fn, iters):
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for i in range(iters):
+        fn(i)
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) / iters * 1e3  # us
+
+
+def rounds(routes, iters):
+    """Three alternating rounds of every route -> [(median, min, max)]."""
+    for fn in routes:
+        for i in range(3):
+            fn(i)
+    torch.cuda.synchronize()
+    ts = [[] for _ in routes]
+    for _ in range(3):
+        for t, fn in zip(ts, routes):
+            t.append(timed(fn, iters))
+    return [(statistics.median(t), min(t), max(t)) for t in ts]
+
+
+def fmt(t):
+    return f"{t[0]:.1f} ({t[1]:.1f}-{t[2]:.1f})"
+
+
+def main():
+    assert torch.cuda.is_available() and ops.have_native()
+    dev = "cuda:0"
+    ts = TS
+    for a in sys.argv[1:]:
+        if a.startswith("--ts="):
+            ts = tuple(int(v) for v in a[5:].split(","))
+
+    def rand(*shape):
+        return (torch.randn(*shape, device=dev) * 0.02).bfloat16()
+
+    router = rand(E, H)
+    norm_w = torch.ones(H, dtype=torch.bfloat16, device=dev)
+    gu_plain = [torch.stack([rand(2 * INTER, H) for _ in range(E)]) for _ in range(MOE_LAYERS)]
+    dn_plain = [torch.stack([rand(H, INTER) for _ in range(E)]) for _ in range(MOE_LAYERS)]
+    gu_pack = [ops.moe_pack_weights(w, True) for w in gu_plain]
+    dn_pack = [ops.moe_pack_weights(w, False) for w in dn_plain]
+    d_gu = [rand(2 * INTER, H) for _ in range(DENSE_LAYERS)]
+    d_dn = [rand(H, INTER) for _ in range(DENSE_LAYERS)]
+    d_int = [
+        ops.swizzle_weight_frag(ops.interleave_gate_up(w))
+        if ops._m256_swiglu_config(256, 2 * INTER, H) is not None else None
+        for w in d_gu
+    ]
+    d_dn_swz = [
+        ops.swizzle_weight_frag(w)
+        if ops._m256_config(256, H, INTER) is not None else None
+        for w in d_dn
+    ]
+    torch.cuda.empty_cache()
+
+    print("T, mf, moe_mlp us, (a) dense 8b MLP us, (b) host-synced expert loop us, "
+          "moe/(a), moe/(b), expert weight bytes / moe_mlp time GB/s, moe_align alone us")
+    for T in ts:
+        x = (torch.randn(T, H, device=dev) * 0.5).bfloat16()
+        res = torch.zeros(T, H, dtype=torch.bfloat16, device=dev)
+        # uniform-random routing: k distinct experts per token
+        ids = torch.rand(T, E, device=dev).argsort(dim=1)[:, :K].int().contiguous()
+        wts = torch.full((T, K), 1.0 / K, device=dev)
+
+        def moe(i):
+            j = i % MOE_LAYERS
+            return ops.moe_mlp(x, router, gu_pack[j], dn_pack[j], K, res, norm_w,
+                               1e-5, ids=ids, weights=wts)
+
+        def dense(i):
+            j = i % DENSE_LAYERS
+            act = ops.swiglu_linear(x, d_gu[j], None, d_int[j])
+            return ops.linear_rmsnorm_residual(act, d_dn[j], d_dn_swz[j], res, norm_w, 1e-5)
+
+        # (b): rows pre-sorted by expert, outside the timed call
+        flat = ids.view(-1).long()
+        order = flat.argsort(stable=True)
+        xs = x[order // K].contiguous()
+        counts_dev = torch.bincount(flat, minlength=E)
+        # y rows come out in sorted order; the combine reads them back in
+        # pair order through the inverse permutation
+        inv = order.argsort()
+        y = torch.empty(T * K, H, dtype=torch.bfloat16, device=dev)
+
+        def loop(i):
+            j = i % MOE_LAYERS
+            counts = counts_dev.tolist()  # the host sync
+            lo = 0
+            for e, n in enumerate(counts):
+                if n:
+                    act = ops.swiglu(ops.linear(xs[lo : lo + n], gu_plain[j][e]))
+                    y[lo : lo + n] = ops.linear(act, dn_plain[j][e])
+                lo += n
+            s = (y[inv].view(T, K, H).float() * wts.unsqueeze(-1)).sum(1).bfloat16()
+            return ops.rmsnorm_residual(s, res, norm_w, 1e-5)
+
+        def align(i):
+            return ops.moe_align(ids, E)
+
+        # windows of 0.1-0.3 s per round
+        iters = 300 if T <= 256 else 40
+        m, a, b = rounds([moe, dense, loop], iters)
+        (al,) = rounds([align], 300)
+        used = len(torch.unique(ids)) * 3 * H * INTER * 2  # bytes of experts hit
+        mf = ops._native().moe_pick_mf(T, K, E)
+        print(
+            f"{T}, {mf}, {fmt(m)}, {fmt(a)}, {fmt(b)}, {m[0] / a[0]:.2f}, "
+            f"{m[0] / b[0]:.2f}, {used / m[0] / 1e3:.0f}, {fmt(al)}",
+            flush=True,
+        )
+
+
+if __name__ == "__main__":
+    main()
