@@ -64,10 +64,32 @@ float* scale_ptr(const c10::optional<torch::Tensor>& s) {
     return s->data_ptr<float>();
 }
 
-void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor weight, double eps) {
+// Shared host-side contract of the two rmsnorm bindings: every tensor bf16
+// on the GPU and contiguous, weight exactly one row wide, out (and the
+// residual) shaped like x. The kernels index all of them by x's T and H.
+void check_rmsnorm_args(const torch::Tensor& out, const torch::Tensor& x,
+                        const torch::Tensor* residual,
+                        const torch::Tensor& weight) {
     check_bf16(x, "x");
     check_bf16(out, "out");
-    TORCH_CHECK(x.is_contiguous() && out.is_contiguous() && weight.is_contiguous());
+    check_bf16(weight, "weight");
+    TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0, "x must be [..., H] with H > 0");
+    TORCH_CHECK(x.is_contiguous() && out.is_contiguous() && weight.is_contiguous(),
+                "x, out and weight must be contiguous");
+    TORCH_CHECK(weight.numel() == x.size(-1),
+                "weight must have H = ", x.size(-1), " elements, got ",
+                weight.numel());
+    TORCH_CHECK(out.sizes() == x.sizes(), "out must have the shape of x");
+    if (residual != nullptr) {
+        check_bf16(*residual, "residual");
+        TORCH_CHECK(residual->is_contiguous(), "residual must be contiguous");
+        TORCH_CHECK(residual->sizes() == x.sizes(),
+                    "residual must have the shape of x");
+    }
+}
+
+void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor weight, double eps) {
+    check_rmsnorm_args(out, x, nullptr, weight);
     const int H = x.size(-1);
     const int T = x.numel() / H;
     CHECK_HIP(launch_rmsnorm(out.data_ptr(), x.data_ptr(), weight.data_ptr(),
@@ -76,8 +98,7 @@ void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor weight, double ep
 
 void rmsnorm_residual(torch::Tensor out, torch::Tensor x, torch::Tensor residual,
                       torch::Tensor weight, double eps) {
-    check_bf16(x, "x");
-    TORCH_CHECK(x.is_contiguous() && out.is_contiguous() && residual.is_contiguous());
+    check_rmsnorm_args(out, x, &residual, weight);
     const int H = x.size(-1);
     const int T = x.numel() / H;
     CHECK_HIP(launch_rmsnorm_residual(out.data_ptr(), x.data_ptr(),

@@ -96,17 +96,36 @@ __global__ void sample_combine_kernel(
 // ---------------------------------------------------------------------------
 // top-k / top-p (nucleus) filtering: mask logits outside the kept set to
 // -inf, in place, one workgroup per row. No sort: a 2048-bin histogram
-// over [max-16, max] locates the coarse threshold bin (counts for top-k,
-// exp-mass for top-p), a second 2048-bin histogram WITHIN that bin
-// refines the cut to 16/2048^2 ~= 3.8e-6 logit granularity — logits
-// closer to the cut than that are kept together (torch's sort breaks
-// such ties arbitrarily too). 4 read passes + 1 write pass over [B, V]
-// vs a full-vocab sort + per-row host loop (the round-1 weakness).
-// Rows with topk[b]==0 and topp[b]>=1 are untouched.
+// over a 16-logit window below the row max locates the coarse threshold
+// bin (counts for top-k, exp-mass for top-p), a second 2048-bin histogram
+// WITHIN that bin refines the cut to 16/2048^2 ~= 3.8e-6 logit granularity.
+//
+// Contract (pinned by tests/elem_cases.py and test_sampling_edges_gpu.py),
+// with c the cut logit of the exact semantics of reference.topk_topp_filter
+// (the k-th largest / the token at which the softmax mass reaches p):
+//  - every logit >= c is kept with its value unchanged, so exact ties at
+//    the cut are kept together (torch's sort breaks them arbitrarily);
+//  - every logit below c by more than one fine bin plus the fp32 rounding
+//    of (max - logit) is masked; anything closer to the cut may be kept;
+//  - top_k is honoured wherever the k-th largest finite logit lies within
+//    TPF_WINDOWS * (16 - 1/128) ~= 143.9 of the row max: when the crossing
+//    is not in the 2047 regular bins of a window, the window is re-based
+//    onto its tail bin with the running count and mass carried, at most
+//    TPF_WINDOWS - 1 times (one more read pass each). Beyond that depth,
+//    or when the row has fewer than k finite logits, nothing is masked;
+//  - with top-p alone a crossing in the first window's tail bin (logits
+//    >= 16 - 1/128 below the max, < 1.2e-7 of the mass) masks nothing: a
+//    superset of the nucleus, and nothing within 16 of the max is lost;
+//  - -inf entries stay -inf and never count towards k;
+//  - rows with topk[b] == 0 (or >= V) and topp[b] >= 1 are untouched.
+// A row whose crossing lies in the first window takes 4 read passes + 1
+// write pass over [B, V], vs a full-vocab sort + per-row host loop (the
+// round-1 weakness).
 // ---------------------------------------------------------------------------
 
 #define TPF_BINS 2048
 #define TPF_RANGE 16.0f  // logits below max-16 carry < 1.2e-7 of the mass
+#define TPF_WINDOWS 9    // 9 * (16 - 1/128) > 128: top-k depth below the max
 
 __launch_bounds__(256)
 __global__ void topk_topp_filter_kernel(
@@ -118,7 +137,7 @@ __global__ void topk_topp_filter_kernel(
     const float p = topp[b];
     const int k = topk[b];
     const bool do_p = p < 1.0f;
-    const bool do_k = k > 0;
+    const bool do_k = k > 0 && k < V;  // the V largest of V: nothing to mask
     if (!do_p && !do_k) return;
     float* row = logits + (size_t)b * V;
     const int tid = threadIdx.x;
@@ -126,7 +145,11 @@ __global__ void topk_topp_filter_kernel(
     __shared__ float s_red[4];
     __shared__ int s_cnt[TPF_BINS];
     __shared__ float s_mass[TPF_BINS];
-    __shared__ float s_out[4];  // [0]=m, [1]=Z, [2]=d_cut, [3]=flag
+    __shared__ float s_cut;       // mask threshold, relative to the window top
+    __shared__ float s_cmass;     // mass above the bin being refined / window
+    __shared__ long long s_ccnt;  // count above it
+    __shared__ int s_bstar;       // coarse bin of the crossing
+    __shared__ int s_flag;        // 0 keep everything, 1 found, 2 re-base
 
     // ---- pass 1: row max ----
     float m = -INFINITY;
@@ -136,61 +159,83 @@ __global__ void topk_topp_filter_kernel(
     __syncthreads();
     m = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
 
-    for (int i = tid; i < TPF_BINS; i += blockDim.x) {
-        s_cnt[i] = 0;
-        s_mass[i] = 0.f;
-    }
-    __syncthreads();
-
-    // ---- pass 2: coarse histogram (+ total softmax mass) ----
     const float scale = TPF_BINS / TPF_RANGE;
-    float zloc = 0.f;
-    for (int i = tid; i < V; i += blockDim.x) {
-        const float d = m - row[i];  // >= 0; +inf-safe (masked rows)
-        const float e = __expf(-d);
-        zloc += e;
-        const int bin = min((int)(d * scale), TPF_BINS - 1);
-        atomicAdd(&s_cnt[bin], 1);
-        atomicAdd(&s_mass[bin], e);
-    }
-    zloc = wave_reduce_sum(zloc);
-    __syncthreads();  // s_red reuse
-    if ((tid & 63) == 0) s_red[tid >> 6] = zloc;
-    __syncthreads();
-    const float Z = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-
-    // ---- coarse scan (thread 0; crossing is near the top in practice) ----
+    const float window_step = (TPF_BINS - 1) / scale;  // tail bin's lower edge
+    float d0 = 0.f;  // distance of the current window's top below the max
+    float Z = 0.f;
     if (tid == 0) {
-        const float needZ = do_p ? p * Z : INFINITY;
-        const long long needK = do_k ? k : 0x7FFFFFFFLL;
-        float cum_mass = 0.f;
-        long long cum_cnt = 0;
-        int bstar = -1;
-        for (int i = 0; i < TPF_BINS - 1; ++i) {
-            cum_mass += s_mass[i];
-            cum_cnt += s_cnt[i];
-            if (cum_mass >= needZ || cum_cnt >= needK) {
-                bstar = i;
-                break;
+        s_cmass = 0.f;
+        s_ccnt = 0;
+    }
+
+    // ---- pass 2 (once per window): coarse histogram (+ total softmax mass
+    // in the first). -inf entries (d = +inf) carry no mass and no rank ----
+    for (int win = 0;; ++win) {
+        for (int i = tid; i < TPF_BINS; i += blockDim.x) {
+            s_cnt[i] = 0;
+            s_mass[i] = 0.f;
+        }
+        __syncthreads();
+        float zloc = 0.f;
+        for (int i = tid; i < V; i += blockDim.x) {
+            const float d = m - row[i];  // >= 0; +inf for masked entries
+            const float rel = d - d0;
+            const bool in_win = rel >= 0.f && d < INFINITY;
+            if (win == 0 || in_win) {  // a re-based window skips what is above it
+                const float e = __expf(-d);
+                zloc += e;  // used by the first window only
+                if (in_win) {
+                    const int bin = min((int)(rel * scale), TPF_BINS - 1);
+                    atomicAdd(&s_cnt[bin], 1);
+                    atomicAdd(&s_mass[bin], e);
+                }
             }
         }
-        s_out[0] = m;
-        s_out[1] = Z;
-        if (bstar < 0) {
-            s_out[3] = 0.f;  // crossing in the tail bin: keep everything
+        if (win == 0) {
+            zloc = wave_reduce_sum(zloc);
+            __syncthreads();  // s_red reuse
+            if ((tid & 63) == 0) s_red[tid >> 6] = zloc;
+            __syncthreads();
+            Z = s_red[0] + s_red[1] + s_red[2] + s_red[3];
         } else {
-            s_out[3] = 1.f;
-            s_out[2] = (float)bstar;  // coarse bin; carry-ins below
-            s_red[0] = cum_mass - s_mass[bstar];  // mass above bstar
-            s_red[1] = (float)(cum_cnt - s_cnt[bstar]);
+            __syncthreads();
         }
+
+        // coarse scan (thread 0; crossing is near the top in practice)
+        if (tid == 0) {
+            const float needZ = do_p ? p * Z : INFINITY;
+            const long long needK = do_k ? k : 0x7FFFFFFFLL;
+            float cum_mass = s_cmass;
+            long long cum_cnt = s_ccnt;
+            int bstar = -1;
+            for (int i = 0; i < TPF_BINS - 1; ++i) {
+                cum_mass += s_mass[i];
+                cum_cnt += s_cnt[i];
+                if (cum_mass >= needZ || cum_cnt >= needK) {
+                    bstar = i;
+                    break;
+                }
+            }
+            if (bstar >= 0) {
+                s_flag = 1;
+                s_bstar = bstar;
+                s_cmass = cum_mass - s_mass[bstar];  // mass above bstar
+                s_ccnt = cum_cnt - s_cnt[bstar];
+            } else if (do_k && s_cnt[TPF_BINS - 1] > 0 && win + 1 < TPF_WINDOWS) {
+                s_flag = 2;  // the k-th largest is in the tail bin: re-base
+                s_cmass = cum_mass;
+                s_ccnt = cum_cnt;
+            } else {
+                s_flag = 0;  // keep everything
+            }
+        }
+        __syncthreads();
+        const int flag = s_flag;
+        if (flag == 0) return;
+        if (flag == 1) break;
+        d0 += window_step;  // exact: a multiple of 1/128 below 2^8
     }
-    __syncthreads();
-    if (s_out[3] == 0.f) return;
-    const int bstar = (int)s_out[2];
-    const float mass_above = s_red[0];
-    const float cnt_above = s_red[1];
-    __syncthreads();
+    const int bstar = s_bstar;
 
     // ---- pass 3: fine histogram within coarse bin bstar ----
     for (int i = tid; i < TPF_BINS; i += blockDim.x) {
@@ -198,24 +243,27 @@ __global__ void topk_topp_filter_kernel(
         s_mass[i] = 0.f;
     }
     __syncthreads();
-    const float d_lo = bstar / scale;  // coarse bin lower edge (distance)
+    const float d_lo = bstar / scale;  // coarse bin lower edge (in-window)
     const float fine_scale = scale * TPF_BINS;
     for (int i = tid; i < V; i += blockDim.x) {
         const float d = m - row[i];
-        const int cb = min((int)(d * scale), TPF_BINS - 1);
-        if (cb == bstar) {
-            const int fb =
-                max(0, min((int)((d - d_lo) * fine_scale), TPF_BINS - 1));
-            atomicAdd(&s_cnt[fb], 1);
-            atomicAdd(&s_mass[fb], __expf(-d));
+        const float rel = d - d0;
+        if (rel >= 0.f && d < INFINITY) {
+            const int cb = min((int)(rel * scale), TPF_BINS - 1);
+            if (cb == bstar) {
+                const int fb =
+                    max(0, min((int)((rel - d_lo) * fine_scale), TPF_BINS - 1));
+                atomicAdd(&s_cnt[fb], 1);
+                atomicAdd(&s_mass[fb], __expf(-d));
+            }
         }
     }
     __syncthreads();
     if (tid == 0) {
-        const float needZ = do_p ? p * s_out[1] : INFINITY;
+        const float needZ = do_p ? p * Z : INFINITY;
         const long long needK = do_k ? k : 0x7FFFFFFFLL;
-        float cum_mass = mass_above;
-        long long cum_cnt = (long long)cnt_above;
+        float cum_mass = s_cmass;
+        long long cum_cnt = s_ccnt;
         int fstar = TPF_BINS - 1;
         for (int i = 0; i < TPF_BINS; ++i) {
             cum_mass += s_mass[i];
@@ -225,15 +273,16 @@ __global__ void topk_topp_filter_kernel(
                 break;
             }
         }
-        // keep d strictly below the fine bin's upper edge
-        s_out[2] = d_lo + (fstar + 1) / fine_scale;
+        // keep what lies strictly below the fine bin's upper edge; relative
+        // to the window top this is below 16 on a 2^-18 grid, exact in fp32
+        s_cut = d_lo + (fstar + 1) / fine_scale;
     }
     __syncthreads();
-    const float d_cut = s_out[2];
+    const float rel_cut = s_cut;
 
     // ---- pass 4: mask ----
     for (int i = tid; i < V; i += blockDim.x) {
-        if (m - row[i] >= d_cut) row[i] = -INFINITY;
+        if ((m - row[i]) - d0 >= rel_cut) row[i] = -INFINITY;
     }
 }
 

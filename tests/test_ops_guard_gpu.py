@@ -240,3 +240,43 @@ def test_fp8_decode_v_scale_guards():
     ocheck("fp8 decode out")
     kscheck("fp8 decode k_scale")
     vscheck("fp8 decode v_scale")
+
+
+def _rms_args(T=4, H=512):
+    x = torch.randn(T, H, dtype=torch.bfloat16, device=DEV)
+    return dict(out=torch.empty_like(x), x=x, residual=torch.randn_like(x),
+                weight=torch.ones(H, dtype=torch.bfloat16, device=DEV))
+
+
+# each entry replaces one argument by one the binding must refuse on the
+# host, before any launch: (argument, replacement from the good arguments)
+_RMS_BAD = {
+    "weight-short": ("weight", lambda a: a["weight"][:256]),
+    "weight-long": ("weight", lambda a: torch.ones(1024, dtype=torch.bfloat16, device=DEV)),
+    "weight-fp32": ("weight", lambda a: a["weight"].float()),
+    "weight-strided": ("weight", lambda a: torch.ones(1024, dtype=torch.bfloat16, device=DEV)[::2]),
+    "out-fp32": ("out", lambda a: a["out"].float()),
+    "out-shape": ("out", lambda a: torch.empty(2, 512, dtype=torch.bfloat16, device=DEV)),
+    "x-fp16": ("x", lambda a: a["x"].half()),
+    "residual-fp32": ("residual", lambda a: a["residual"].float()),
+    "residual-shape": ("residual", lambda a: a["residual"][:2]),
+    "residual-strided": ("residual", lambda a: torch.randn(4, 1024, dtype=torch.bfloat16, device=DEV)[:, ::2]),
+}
+
+
+@pytest.mark.parametrize("bad", sorted(_RMS_BAD))
+def test_rmsnorm_bindings_refuse_bad_arguments(bad):
+    """Host-side argument checks of the two rmsnorm bindings: a mismatched
+    tensor raises before anything is launched, and nothing is written."""
+    name, make = _RMS_BAD[bad]
+    a = _rms_args()
+    a[name] = make(a)
+    before = {k: v.clone() for k, v in a.items()}
+    if name != "residual":
+        with pytest.raises(RuntimeError):
+            ops._native().rmsnorm(a["out"], a["x"], a["weight"], 1e-5)
+    with pytest.raises(RuntimeError):
+        ops._native().rmsnorm_residual(a["out"], a["x"], a["residual"], a["weight"], 1e-5)
+    torch.cuda.synchronize()
+    for k in ("x", "residual"):
+        assert torch.equal(a[k], before[k]), f"{k} was written despite the refusal"
