@@ -216,7 +216,8 @@ def check_moe_supported(
             "mixture-of-experts models (num_experts > 0) are not supported "
             "with tensor parallelism (tp_size > 1) yet"
         )
-    if weight_dtype != "auto":
+    # "mxfp4" is served (ops/csrc/moe_w4.hip); fp8 experts are not yet
+    if weight_dtype not in ("auto", "mxfp4"):
         raise NotImplementedError(
             "mixture-of-experts models (num_experts > 0) are not supported "
             f"with quantised weights (weight_dtype={weight_dtype!r}) yet"

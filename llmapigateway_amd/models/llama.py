@@ -109,12 +109,14 @@ class LlamaModel:
         # "mxfp4": the same four as OCP MXFP4 — e2m1 nibbles plus one e8m0
         # scale per 32 k of a row (fragment-major,
         # ops.swizzle_weight_frag_mxfp4) — run through ops.linear_w4
-        # mixture of experts: not with TP, quantised weights or adapters yet
+        # mixture of experts: not with TP, fp8 weights or adapters yet.
+        # "mxfp4" there: qkv/o as above, the router stays bf16, the expert
+        # stacks are MXFP4 panels run through ops.moe_mlp (ops/csrc/moe_w4.hip)
         check_moe_supported(config, tp_size, weight_dtype, max_loras)
         if config.num_experts:
             ops.moe_check_shapes(
                 config.num_experts, config.experts_per_token,
-                config.hidden_size, config.intermediate_size,
+                config.hidden_size, config.intermediate_size, weight_dtype,
             )
         self.weight_dtype = weight_dtype
         self.config = config
@@ -230,10 +232,34 @@ class LlamaModel:
         the expert stacks in place of gate_up/down, drawn in a fixed order
         (router, every expert's gate_up, every expert's down). On the GPU
         the stacks are held packed only (ops.moe_pack_weights: ONE resident
-        copy, no twins); on the CPU they stay plain [E, 2I, H] / [E, H, I]."""
+        copy, no twins); on the CPU they stay plain [E, 2I, H] / [E, H, I].
+
+        weight_dtype="mxfp4" draws the same weights in the same order, so the
+        model is the quantisation of the bf16 model of that seed: qkv and o
+        as in a dense layer, the router bf16, and every expert matrix
+        quantised as it is drawn (no bf16 stack ever exists) into
+        `experts_gate_up_q4/_s4` and `experts_down_q4/_s4`."""
         c = self.config
         E, hidden, inter = c.num_experts, c.hidden_size, c.intermediate_size
         router = mk(E, hidden, std)
+        if self.weight_dtype == "mxfp4":
+            layer = {
+                "input_norm": torch.ones(hidden, dtype=self.dtype, device=self.device),
+                "post_norm": torch.ones(hidden, dtype=self.dtype, device=self.device),
+                "router": router,
+            }
+            for name, full in (("qkv", qkv), ("o", o)):
+                self._store_w4(layer, name, *ops.mxfp4_quantize_weight(full))
+            for name, rows, cols, w_std in (
+                ("experts_gate_up", 2 * inter, hidden, std),
+                ("experts_down", hidden, inter, out_std),
+            ):
+                q = torch.empty(E, rows, cols // 2, dtype=torch.uint8, device=self.device)
+                s = torch.empty(E, rows, cols // 32, dtype=torch.uint8, device=self.device)
+                for e in range(E):
+                    q[e], s[e] = ops.mxfp4_quantize_weight(mk(rows, cols, w_std))
+                self._store_experts_w4(layer, name, q, s)
+            return layer
         gate_up = torch.empty(E, 2 * inter, hidden, dtype=self.dtype, device=self.device)
         for e in range(E):
             gate_up[e] = mk(2 * inter, hidden, std)
@@ -307,6 +333,13 @@ class LlamaModel:
             packed, s
         )
 
+    def _store_experts_w4(self, layer, name: str, q: torch.Tensor, s: torch.Tensor) -> None:
+        """An MXFP4 expert stack ([E, N, K/2], [E, N, K/32]): the panels of
+        ops.moe_pack_weights_mxfp4 on the GPU, plain on the CPU."""
+        if self.device.type == "cuda":
+            q, s = ops.moe_pack_weights_mxfp4(q, s, name == "experts_gate_up")
+        layer[name + "_q4"], layer[name + "_s4"] = q, s
+
     def _reserve_w8_buffer(self) -> None:
         """The M > 256 route dequantises into one per-device bf16 buffer:
         size it for the largest projection now, so captured graphs never
@@ -323,6 +356,7 @@ class LlamaModel:
                 layer[name + key].numel() * per_byte
                 for layer in self.layers
                 for name in ("qkv", "o", "gate_up", "down")
+                if name + key in layer  # an MoE layer has qkv and o only
             ),
         )
 
@@ -346,7 +380,7 @@ class LlamaModel:
                 "quantize_weights_ works on an unsharded model; under tensor "
                 f"parallelism construct with weight_dtype={mode!r}"
             )
-        names = ("qkv", "o", "gate_up", "down")
+        names = ("qkv", "o") if self.config.num_experts else ("qkv", "o", "gate_up", "down")
         if mode == "mxfp4":
             quantize, dequantize, store = (
                 ops.mxfp4_quantize_weight, ops.mxfp4_dequantize_weight, self._store_w4
@@ -365,12 +399,35 @@ class LlamaModel:
                 else:
                     del layer[name]
                     store(layer, name, q, s)
+            if self.config.num_experts:
+                self._quantize_experts_(layer, simulate)
         if simulate:
             self._build_twins()
         else:
             self.weight_dtype = mode
             self._reserve_w8_buffer()
         return self
+
+    def _quantize_experts_(self, layer, simulate: bool) -> None:
+        """The expert stacks of one layer to MXFP4, expert by expert.
+        simulate: their dequantised values, held as the bf16 model holds
+        them (repacked for the bf16 kernel on the GPU)."""
+        cuda = self.device.type == "cuda"
+        for name in ("experts_gate_up", "experts_down"):
+            gate_up = name == "experts_gate_up"
+            w = layer.pop(name)
+            if cuda:
+                w = ops.moe_unpack_weights(w, gate_up)
+            qs = [ops.mxfp4_quantize_weight(w[e]) for e in range(w.shape[0])]
+            del w
+            if simulate:
+                w = torch.stack([ops.mxfp4_dequantize_weight(q, s, self.dtype) for q, s in qs])
+                layer[name] = ops.moe_pack_weights(w, gate_up) if cuda else w
+            else:
+                self._store_experts_w4(
+                    layer, name, torch.stack([q for q, _ in qs]),
+                    torch.stack([s for _, s in qs]),
+                )
 
     def _build_twins(self) -> None:
         # Fragment-major twins of the decode projections for the
@@ -744,6 +801,15 @@ class LlamaModel:
                 residual, layer["post_norm"],
             )
             if c.num_experts:
+                if self.weight_dtype == "mxfp4":
+                    x, residual = ops.moe_mlp(
+                        x, layer["router"], layer["experts_gate_up_q4"],
+                        layer["experts_down_q4"], c.experts_per_token, residual,
+                        next_norm, c.rms_eps,
+                        s_gate_up=layer["experts_gate_up_s4"],
+                        s_down=layer["experts_down_s4"],
+                    )
+                    continue
                 x, residual = ops.moe_mlp(
                     x, layer["router"], layer["experts_gate_up"],
                     layer["experts_down"], c.experts_per_token, residual,

@@ -55,6 +55,10 @@ from .reference import (  # re-export (MXFP4 weight quantisation scheme)
     unswizzle_weight_frag_mxfp4,
 )
 from .reference import moe_unpack_weights  # re-export (inverse of moe_pack_weights)
+from .reference import (  # re-export (MXFP4 expert layout of csrc/moe_w4.hip)
+    moe_pack_weights_mxfp4,
+    moe_unpack_weights_mxfp4,
+)
 
 _C = None
 _C_ERR: Optional[str] = None
@@ -1257,10 +1261,13 @@ def lora_add(
 MOE_MAX_EXPERTS = 64  # keep in sync with MOE_MAX_E / MOE_MAX_K in moe.hip
 MOE_MAX_TOPK = 8
 MOE_MAX_HIDDEN = 8192  # moe_route: four x rows in 64 KiB of dynamic LDS
+MOE_W4_GROUP = reference.MOE_W4_GROUP  # k of one group of the MXFP4 expert layout
+MOE_W4_RING_DEPTH = 4  # k groups; keep in sync with MW_D in moe_w4.hip
 
 
-def moe_check_shapes(E: int, k: int, H: int, inter: int) -> None:
-    """The shapes the MoE kernels serve; anything else is an error."""
+def moe_check_shapes(E: int, k: int, H: int, inter: int, weight_dtype: str = "auto") -> None:
+    """The shapes the MoE kernels serve; anything else is an error. MXFP4
+    expert weights are laid out in k groups of 128 (csrc/moe_w4.hip)."""
     if not (2 <= E <= MOE_MAX_EXPERTS):
         raise ValueError(f"MoE needs 2 <= num_experts <= {MOE_MAX_EXPERTS}, got {E}")
     if not (1 <= k <= min(E, MOE_MAX_TOPK)):
@@ -1277,6 +1284,11 @@ def moe_check_shapes(E: int, k: int, H: int, inter: int) -> None:
         raise ValueError(
             f"MoE needs hidden size <= {MOE_MAX_HIDDEN} (the router holds four "
             f"x rows in 64 KiB of LDS), got {H}"
+        )
+    if weight_dtype == "mxfp4" and (H % MOE_W4_GROUP or inter % MOE_W4_GROUP):
+        raise ValueError(
+            f"MoE with mxfp4 expert weights needs hidden and intermediate sizes "
+            f"in multiples of {MOE_W4_GROUP}, got {H} and {inter}"
         )
 
 
@@ -1329,11 +1341,16 @@ def moe_align(ids: torch.Tensor, E: int, mf: Optional[int] = None) -> MoePlan:
 def moe_gate_up_swiglu(
     x: torch.Tensor, ids: torch.Tensor, w_gate_up: torch.Tensor,
     plan: Optional[MoePlan] = None, out: Optional[torch.Tensor] = None,
+    s_gate_up: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """swiglu(x[t] @ w_gate_up[ids[t, j]].T) per pair. CPU: [T*k, I] in pair
     order. GPU: w_gate_up packed, act [plan.cap, I] in sorted order (padding
-    rows are not written), into `out` when given."""
+    rows are not written), into `out` when given. With s_gate_up the weights
+    are MXFP4: plain ([E, 2I, H/2], [E, 2I, H/32]) on the CPU, the panels of
+    moe_pack_weights_mxfp4 on the GPU (csrc/moe_w4.hip)."""
     if not x.is_cuda:
+        if s_gate_up is not None:
+            w_gate_up = reference.moe_dequantize_experts_mxfp4(w_gate_up, s_gate_up, x.dtype)
         return reference.moe_gate_up_swiglu(x, ids, w_gate_up)
     if plan is None:
         raise ValueError("moe_gate_up_swiglu on the GPU needs moe_align's plan")
@@ -1342,6 +1359,10 @@ def moe_gate_up_swiglu(
     act = out
     if act is None:
         act = torch.empty(plan.cap, inter, dtype=x.dtype, device=x.device)
+    if s_gate_up is not None:
+        _native().moe_gemm_w4(act, x, w_gate_up, s_gate_up, plan.sorted_pairs,
+                              plan.tile_expert, None, 0, plan.mf, k, ids.numel())
+        return act
     _native().moe_gemm(act, x, w_gate_up, plan.sorted_pairs, plan.tile_expert,
                        None, 0, plan.mf, k, ids.numel())
     return act
@@ -1350,12 +1371,15 @@ def moe_gate_up_swiglu(
 def moe_down(
     act: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor,
     w_down: torch.Tensor, plan: Optional[MoePlan] = None,
-    out: Optional[torch.Tensor] = None,
+    out: Optional[torch.Tensor] = None, s_down: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """y_pair [T*k, H] = weights[t, j] * (act row @ w_down[ids[t, j]].T) in
     pair order. GPU: act in the plan's sorted order, w_down packed; into
-    `out` when given."""
+    `out` when given. With s_down the weights are MXFP4, as in
+    moe_gate_up_swiglu."""
     if not act.is_cuda:
+        if s_down is not None:
+            w_down = reference.moe_dequantize_experts_mxfp4(w_down, s_down, act.dtype)
         return reference.moe_down(act, ids, weights, w_down)
     if plan is None:
         raise ValueError("moe_down on the GPU needs moe_align's plan")
@@ -1363,6 +1387,11 @@ def moe_down(
     if y_pair is None:
         y_pair = torch.empty(ids.numel(), w_down.shape[2] * 16, dtype=act.dtype,
                              device=act.device)
+    if s_down is not None:
+        _native().moe_gemm_w4(y_pair, act, w_down, s_down, plan.sorted_pairs,
+                              plan.tile_expert, weights, 1, plan.mf,
+                              ids.shape[1], ids.numel())
+        return y_pair
     _native().moe_gemm(y_pair, act, w_down, plan.sorted_pairs, plan.tile_expert,
                        weights, 1, plan.mf, ids.shape[1], ids.numel())
     return y_pair
@@ -1386,11 +1415,19 @@ def moe_mlp(
     w_down: torch.Tensor, k: int, residual: torch.Tensor,
     norm_w: torch.Tensor, eps: float = 1e-5,
     ids: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+    s_gate_up: Optional[torch.Tensor] = None, s_down: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """The MoE layer tail -> (normed, residual): five launches on the GPU
     (route, align, gate_up+swiglu, down, combine+norm), none of which reads
-    device data on the host. ids/weights given: the router is skipped."""
+    device data on the host. ids/weights given: the router is skipped.
+    s_gate_up / s_down given (both or neither): MXFP4 expert weights, see
+    moe_gate_up_swiglu."""
+    if (s_gate_up is None) != (s_down is None):
+        raise ValueError("moe_mlp takes s_gate_up and s_down together")
     if not x.is_cuda:
+        if s_gate_up is not None:
+            w_gate_up = reference.moe_dequantize_experts_mxfp4(w_gate_up, s_gate_up, x.dtype)
+            w_down = reference.moe_dequantize_experts_mxfp4(w_down, s_down, x.dtype)
         if ids is None:
             return reference.moe_mlp(x, w_router, w_gate_up, w_down, k, residual,
                                      norm_w, eps)
@@ -1400,8 +1437,8 @@ def moe_mlp(
     if ids is None:
         ids, weights = moe_route(x, w_router, k)
     plan = moe_align(ids, w_gate_up.shape[0])
-    act = moe_gate_up_swiglu(x, ids, w_gate_up, plan)
-    y_pair = moe_down(act, ids, weights, w_down, plan)
+    act = moe_gate_up_swiglu(x, ids, w_gate_up, plan, s_gate_up=s_gate_up)
+    y_pair = moe_down(act, ids, weights, w_down, plan, s_down=s_down)
     return moe_combine_rmsnorm_residual(y_pair, residual, norm_w, eps, k)
 
 
@@ -1473,6 +1510,8 @@ __all__ = [
     "moe_check_shapes",
     "moe_pack_weights",
     "moe_unpack_weights",
+    "moe_pack_weights_mxfp4",
+    "moe_unpack_weights_mxfp4",
     "moe_cap",
     "moe_route",
     "moe_align",

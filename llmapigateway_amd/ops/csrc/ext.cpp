@@ -30,6 +30,7 @@ hipError_t launch_moe_route(int*, float*, const void*, const void*, int, int, in
 hipError_t launch_moe_align(int*, int*, const int*, int, int, int, int, hipStream_t);
 hipError_t launch_moe_gemm(void*, const void*, const void*, const int*, const int*, const float*, int, int, int, int, int, int, hipStream_t);
 hipError_t launch_moe_combine_norm(void*, void*, const void*, const void*, float, int, int, int, hipStream_t);
+hipError_t launch_moe_gemm_w4(void*, const void*, const void*, const void*, const int*, const int*, const float*, int, int, int, int, int, int, hipStream_t);
 }
 
 namespace {
@@ -755,6 +756,63 @@ void moe_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w,
                               current_stream()));
 }
 
+// moe_gemm with MXFP4 expert weights (ops.moe_pack_weights_mxfp4):
+// wq [E, K/128, N/16, 64, 16] nibble bytes, ws [E, K/128, N/16, 16, 4] scale
+// bytes
+void moe_gemm_w4(torch::Tensor out, torch::Tensor a, torch::Tensor wq,
+                 torch::Tensor ws, torch::Tensor sorted_pairs,
+                 torch::Tensor tile_expert,
+                 c10::optional<torch::Tensor> rweights, int64_t epi, int64_t mf,
+                 int64_t k, int64_t P) {
+    check_bf16(out, "out");
+    check_bf16(a, "a");
+    check_i32(sorted_pairs, "sorted_pairs");
+    check_i32(tile_expert, "tile_expert");
+    TORCH_CHECK(wq.is_cuda() && ws.is_cuda() && wq.scalar_type() == torch::kUInt8 &&
+                ws.scalar_type() == torch::kUInt8 && wq.device() == a.device() &&
+                ws.device() == a.device(),
+                "wq / ws must be uint8 tensors on the device of a");
+    TORCH_CHECK(epi == 0 || epi == 1, "epi must be 0 (swiglu) or 1 (down)");
+    TORCH_CHECK(mf == 1 || mf == 2 || mf == 4, "mf must be 1, 2 or 4");
+    TORCH_CHECK(out.is_contiguous() && a.is_contiguous() && wq.is_contiguous() &&
+                ws.is_contiguous() && out.dim() == 2 && a.dim() == 2);
+    TORCH_CHECK(wq.dim() == 5 && wq.size(3) == 64 && wq.size(4) == 16,
+                "wq must be packed [E, K/128, N/16, 64, 16] (ops.moe_pack_weights_mxfp4)");
+    const int64_t E = wq.size(0), K = wq.size(1) * 128, N = wq.size(2) * 16;
+    TORCH_CHECK(ws.dim() == 5 && ws.size(0) == E && ws.size(1) == K / 128 &&
+                ws.size(2) == N / 16 && ws.size(3) == 16 && ws.size(4) == 4,
+                "ws must be packed [E, K/128, N/16, 16, 4] for the E, N, K of wq");
+    const int64_t BM = 16 * mf, tiles = tile_expert.numel(), cap = tiles * BM;
+    check_moe_shape(E, k);
+    TORCH_CHECK(sorted_pairs.numel() == cap, "sorted_pairs must be [cap]");
+    TORCH_CHECK(a.size(1) == K, "a must be [rows, K]");
+    // P = T * k pairs; only the down epilogue reads the routing weights
+    const float* rw = nullptr;
+    if (epi == 1) {
+        TORCH_CHECK(rweights.has_value() && rweights->is_cuda() &&
+                    rweights->scalar_type() == torch::kFloat32 &&
+                    rweights->is_contiguous() && rweights->numel() == P,
+                    "weights must be fp32 [T, k]");
+        rw = rweights->data_ptr<float>();
+    }
+    TORCH_CHECK(P > 0 && P % k == 0 && cap >= P + E * (BM - 1),
+                "cap too small for the pairs");
+    if (epi == 0) {
+        TORCH_CHECK(N % 128 == 0, "intermediate size must be a multiple of 64");
+        TORCH_CHECK(a.size(0) == P / k, "x must be [T, H]");
+        TORCH_CHECK(out.size(0) == cap && out.size(1) == N / 2, "act must be [cap, I]");
+    } else {
+        TORCH_CHECK(N % 64 == 0, "hidden size must be a multiple of 64");
+        TORCH_CHECK(a.size(0) == cap, "act must be [cap, I]");
+        TORCH_CHECK(out.size(0) == P && out.size(1) == N, "y_pair must be [T*k, H]");
+    }
+    CHECK_HIP(launch_moe_gemm_w4(out.data_ptr(), a.data_ptr(), wq.data_ptr(),
+                                 ws.data_ptr(), sorted_pairs.data_ptr<int>(),
+                                 tile_expert.data_ptr<int>(), rw, (int)epi,
+                                 (int)mf, (int)tiles, (int)N, (int)K, (int)k,
+                                 current_stream()));
+}
+
 void moe_combine_norm(torch::Tensor normed, torch::Tensor residual,
                       torch::Tensor y_pair, torch::Tensor norm_w, double eps,
                       int64_t k) {
@@ -782,6 +840,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("moe_route", &moe_route, "MoE router: softmax top-k ids and weights per row");
     m.def("moe_align", &moe_align, "MoE counting sort of the pairs by expert, BM-padded");
     m.def("moe_gemm", &moe_gemm, "grouped expert GEMM (epi 0: gate_up+swiglu, 1: down)");
+    m.def("moe_gemm_w4", &moe_gemm_w4,
+          "grouped expert GEMM with MXFP4 expert weights (W4A16)");
     m.def("moe_combine_norm", &moe_combine_norm,
           "sum of a token's k expert rows + residual add + RMSNorm");
     m.def("lora_shrink", &lora_shrink,

@@ -443,6 +443,77 @@ def linear_w4(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor) -> tor
     return (x.float() @ w.T).to(x.dtype)
 
 
+MOE_W4_GROUP = 128  # k of one group of the MXFP4 expert layout
+
+
+def moe_pack_weights_mxfp4(packed: torch.Tensor, scale: torch.Tensor, gate_up: bool):
+    """MXFP4 expert stack (packed [E, N, K/2], scale [E, N, K/32], both
+    uint8, every expert as mxfp4_quantize_weight writes it) -> the resident
+    GPU layout of csrc/moe_w4.hip, k grouped by 128:
+
+    q_panel [E, K/128, N/16, 64, 16]: [e][g][n16][lane][j*4 + b] =
+        packed[e][n16*16 + (lane & 15)][g*64 + j*16 + (lane >> 4)*4 + b] —
+        dword j is the lane's share (8 nibbles, k ascending) of the
+        mfma_f32_16x16x32_bf16 B fragment of k32 step j of the group, the
+        lane order of moe_pack_weights; one 16-byte load per lane and group.
+    s_panel [E, K/128, N/16, 16, 4]: [e][g][n16][r][j] =
+        scale[e][n16*16 + r][g*4 + j] — the four block scales of a column
+        and group as one dword.
+
+    gate_up=True first permutes the rows of nibbles and scales alike to the
+    block-16 gate/up interleave of moe_pack_weights."""
+    E, N, K = packed.shape[0], packed.shape[1], packed.shape[2] * 2
+    if N % 64 or K % MOE_W4_GROUP:
+        raise ValueError(
+            f"MXFP4 expert weights need N in multiples of 64 and K in multiples "
+            f"of {MOE_W4_GROUP}, got {(N, K)}"
+        )
+    if scale.shape != (E, N, K // MXFP4_BLOCK):
+        raise ValueError(f"scale must be [E, N, K/32], got {tuple(scale.shape)}")
+    if gate_up:
+        packed = packed.view(E, 2, N // 32, 16, K // 2).transpose(1, 2).reshape(E, N, K // 2)
+        scale = scale.view(E, 2, N // 32, 16, K // 32).transpose(1, 2).reshape(E, N, K // 32)
+    G = K // MOE_W4_GROUP
+    # byte = g*64 + j*16 + c*4 + b, n = n16*16 + r; lane = c*16 + r
+    q_panel = (
+        packed.view(E, N // 16, 16, G, 4, 4, 4)
+        .permute(0, 3, 1, 5, 2, 4, 6)
+        .reshape(E, G, N // 16, 64, 16)
+        .contiguous()
+    )
+    s_panel = (
+        scale.view(E, N // 16, 16, G, 4).permute(0, 3, 1, 2, 4).contiguous()
+    )
+    return q_panel, s_panel
+
+
+def moe_unpack_weights_mxfp4(q_panel: torch.Tensor, s_panel: torch.Tensor, gate_up: bool):
+    """Inverse of moe_pack_weights_mxfp4: -> (packed [E, N, K/2], scale
+    [E, N, K/32])."""
+    E, G, n16 = q_panel.shape[:3]
+    N, K = n16 * 16, G * MOE_W4_GROUP
+    packed = (
+        q_panel.view(E, G, n16, 4, 16, 4, 4)
+        .permute(0, 2, 4, 1, 5, 3, 6)
+        .reshape(E, N, K // 2)
+    )
+    scale = s_panel.permute(0, 2, 3, 1, 4).reshape(E, N, K // 32)
+    if gate_up:
+        packed = packed.view(E, N // 32, 2, 16, K // 2).transpose(1, 2).reshape(E, N, K // 2)
+        scale = scale.view(E, N // 32, 2, 16, K // 32).transpose(1, 2).reshape(E, N, K // 32)
+    return packed.contiguous(), scale.contiguous()
+
+
+def moe_dequantize_experts_mxfp4(
+    packed: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype = torch.bfloat16
+) -> torch.Tensor:
+    """MXFP4 expert stack ([E, N, K/2], [E, N, K/32]) -> [E, N, K], expert by
+    expert with mxfp4_dequantize_weight (exact for bf16 and wider)."""
+    return torch.stack(
+        [mxfp4_dequantize_weight(packed[e], scale[e], dtype) for e in range(packed.shape[0])]
+    )
+
+
 def kv_cache_write(
     k: torch.Tensor,
     v: torch.Tensor,

@@ -14,12 +14,16 @@ with uniform-random routing, beside two baselines at the same T:
 
 The last column times moe_align alone (warm, the sort of the T*k pairs).
 
+--weight-dtype=auto,mxfp4 also times moe_mlp on the MXFP4 quantisation of the
+same expert weights (csrc/moe_w4.hip) in the same alternating rounds and
+prints a second line per T.
+
 As in tools/lora_bench.py every route cycles through several layers' worth of
 weights (each layer's experts are 2.8 GB, far beyond the 256 MB L3), routes
 alternate, three rounds each; the median round is reported with the min-max
 of the three. Run on the GPU box:
 
-    python tools/moe_bench.py [--ts=16,64,256,4096]
+    python tools/moe_bench.py [--ts=16,64,256,4096] [--weight-dtype=auto,mxfp4]
 """
 
 import os
@@ -68,10 +72,15 @@ def fmt(t):
 def main():
     assert torch.cuda.is_available() and ops.have_native()
     dev = "cuda:0"
-    ts = TS
+    ts, dtypes = TS, ("auto",)
     for a in sys.argv[1:]:
         if a.startswith("--ts="):
             ts = tuple(int(v) for v in a[5:].split(","))
+        elif a.startswith("--weight-dtype="):
+            dtypes = tuple(a[15:].split(","))
+        else:
+            raise SystemExit(f"unknown argument {a}")
+    assert set(dtypes) <= {"auto", "mxfp4"} and "auto" in dtypes, dtypes
 
     def rand(*shape):
         return (torch.randn(*shape, device=dev) * 0.02).bfloat16()
@@ -82,6 +91,16 @@ def main():
     dn_plain = [torch.stack([rand(H, INTER) for _ in range(E)]) for _ in range(MOE_LAYERS)]
     gu_pack = [ops.moe_pack_weights(w, True) for w in gu_plain]
     dn_pack = [ops.moe_pack_weights(w, False) for w in dn_plain]
+
+    def pack_w4(w, gate_up):  # expert by expert: the quantiser works in fp32
+        qs = [ops.mxfp4_quantize_weight(w[e]) for e in range(E)]
+        return ops.moe_pack_weights_mxfp4(
+            torch.stack([q for q, _ in qs]), torch.stack([s for _, s in qs]), gate_up
+        )
+
+    w4 = "mxfp4" in dtypes
+    gu_w4 = [pack_w4(w, True) for w in gu_plain] if w4 else []
+    dn_w4 = [pack_w4(w, False) for w in dn_plain] if w4 else []
     d_gu = [rand(2 * INTER, H) for _ in range(DENSE_LAYERS)]
     d_dn = [rand(H, INTER) for _ in range(DENSE_LAYERS)]
     d_int = [
@@ -109,6 +128,12 @@ def main():
             j = i % MOE_LAYERS
             return ops.moe_mlp(x, router, gu_pack[j], dn_pack[j], K, res, norm_w,
                                1e-5, ids=ids, weights=wts)
+
+        def moe_w4(i):
+            j = i % MOE_LAYERS
+            return ops.moe_mlp(x, router, gu_w4[j][0], dn_w4[j][0], K, res, norm_w,
+                               1e-5, ids=ids, weights=wts,
+                               s_gate_up=gu_w4[j][1], s_down=dn_w4[j][1])
 
         def dense(i):
             j = i % DENSE_LAYERS
@@ -142,7 +167,9 @@ def main():
 
         # windows of 0.1-0.3 s per round
         iters = 300 if T <= 256 else 40
-        m, a, b = rounds([moe, dense, loop], iters)
+        m, a, b, *q = rounds(
+            [moe, dense, loop] + ([moe_w4] if w4 else []), iters
+        )
         (al,) = rounds([align], 300)
         used = len(torch.unique(ids)) * 3 * H * INTER * 2  # bytes of experts hit
         mf = ops._native().moe_pick_mf(T, K, E)
@@ -151,6 +178,14 @@ def main():
             f"{m[0] / b[0]:.2f}, {used / m[0] / 1e3:.0f}, {fmt(al)}",
             flush=True,
         )
+        for t in q:
+            # disjoint: the two min-max ranges do not overlap
+            print(
+                f"  mxfp4: moe_mlp {fmt(t)} us, bf16/mxfp4 "
+                f"{m[0] / t[0]:.2f}, disjoint {t[2] < m[1] or m[2] < t[1]}, expert "
+                f"weight bytes / time {used * 4.25 / 16 / t[0] / 1e3:.0f} GB/s",
+                flush=True,
+            )
 
 
 if __name__ == "__main__":
