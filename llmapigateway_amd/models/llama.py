@@ -613,11 +613,12 @@ class LlamaModel:
                     widths[seg], rank).normal_(0.0, 0.02, generator=gen)
         return out
 
-    def _linear_lora(self, x, layer, name: str, stacks, adapter_ids) -> torch.Tensor:
+    def _linear_lora(self, x, layer, name: str, stacks, adapter_ids, plan=None) -> torch.Tensor:
         """Base projection, then the per-row adapter delta on its bf16
-        output: the same on every weight_dtype route."""
+        output: the same on every weight_dtype route. `plan` is the
+        forward's ops.lora_plan (rows sorted by adapter), or None."""
         y = self._linear(x, layer, name)
-        return ops.lora_add(y, x, stacks[name], adapter_ids)
+        return ops.lora_add(y, x, stacks[name], adapter_ids, plan)
 
     def param_bytes(self) -> int:
         tensors = [self.embed, self.final_norm]
@@ -707,7 +708,7 @@ class LlamaModel:
         (profiles/r10_multi_lora.md)."""
         c = self.config
         stacks_all = self.lora_layers if self.max_loras else None
-        aid = None
+        aid = lplan = None
         if stacks_all is not None:
             aid = batch.adapter_ids
             if aid is None:
@@ -715,6 +716,9 @@ class LlamaModel:
                     (batch.token_ids.shape[0],), -1, dtype=torch.int32,
                     device=self.device,
                 )
+            # the sorted order depends on the adapter ids alone: one plan
+            # for every projection of every layer (None: vector kernels)
+            lplan = ops.lora_plan(aid, self.lora_ranks)
         ksc = k_scales if k_scales is not None else [None] * len(self.layers)
         vsc = v_scales if v_scales is not None else [None] * len(self.layers)
         h = F.embedding(batch.token_ids, self.embed)
@@ -730,7 +734,7 @@ class LlamaModel:
             if lora is None:
                 qkv = self._linear(x, layer, "qkv")
             else:
-                qkv = self._linear_lora(x, layer, "qkv", lora, aid)
+                qkv = self._linear_lora(x, layer, "qkv", lora, aid, lplan)
             q, k, v = qkv.split([c.q_size, c.kv_size, c.kv_size], dim=-1)
             q = q.view(T, c.num_heads, c.head_dim)
             k = k.view(T, c.num_kv_heads, c.head_dim)
@@ -786,13 +790,13 @@ class LlamaModel:
             if lora is not None:
                 x, residual = ops.rmsnorm_residual(
                     self._linear_lora(
-                        attn.reshape(T, c.q_size), layer, "o", lora, aid
+                        attn.reshape(T, c.q_size), layer, "o", lora, aid, lplan
                     ),
                     residual, layer["post_norm"], c.rms_eps,
                 )
-                act = ops.swiglu(self._linear_lora(x, layer, "gate_up", lora, aid))
+                act = ops.swiglu(self._linear_lora(x, layer, "gate_up", lora, aid, lplan))
                 x, residual = ops.rmsnorm_residual(
-                    self._linear_lora(act, layer, "down", lora, aid),
+                    self._linear_lora(act, layer, "down", lora, aid, lplan),
                     residual, next_norm, c.rms_eps,
                 )
                 continue

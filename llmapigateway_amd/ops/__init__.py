@@ -1241,11 +1241,160 @@ def lora_expand(
     return y
 
 
+# ---- segmented multi-LoRA: rows sorted by slot, MFMA tiles (csrc/lora_seg.hip) ----
+# lora_add takes the segmented pair from this many rows on; below it (and for
+# shapes the segmented kernels do not serve) the vector pair above runs. The
+# default is the smallest measured T at which the segmented pair won on every
+# llama-3-8b projection (profiles/r13_lora_segmented.md).
+LORA_SEG_MIN_T = int(os.environ.get("LLMAPI_LORA_SEG_MIN_T", "4096"))
+LORA_SEG_MAX_SLOTS = 64  # keep in sync with LS_MAX_S in lora_seg.hip
+
+
+class LoraPlan:
+    """lora_align's result. sorted_rows [cap] int32: row index, every slot's
+    rows together in ascending order and padded with -1 to a multiple of
+    BM = 16*mf; tile_slot [cap / BM] int32: slot of a row tile, -1 = unused."""
+
+    def __init__(self, sorted_rows, tile_slot, mf: int, T: int):
+        self.sorted_rows, self.tile_slot, self.mf = sorted_rows, tile_slot, mf
+        self.cap = sorted_rows.numel()
+        self.T = T  # rows of the batch it sorts: sorted_rows indexes [0, T)
+
+    def check(self, t: torch.Tensor, what: str) -> None:
+        if t.shape[0] != self.T:
+            raise ValueError(
+                f"{what} has {t.shape[0]} rows, the LoraPlan sorts {self.T}"
+            )
+
+
+def lora_cap(T: int, S: int, mf: int) -> int:
+    """Rows of the sorted order for T rows in the worst case: every slot may
+    pad up to BM - 1 rows; rounded up to whole tiles (as moe_cap)."""
+    return moe_cap(T, S, mf)
+
+
+# plan buffers, one pair per (device, T, S, mf) and never freed: a captured
+# graph replays lora_align and its readers into these addresses
+_lora_plans: dict = {}
+_lora_tpart = _Scratch(torch.float32)  # split-K partials of lora_shrink_seg
+
+
+def lora_align(
+    adapter_ids: torch.Tensor, ranks: torch.Tensor, mf: Optional[int] = None
+) -> LoraPlan:
+    """GPU only: stable sort of the T rows by adapter slot (S = len(ranks));
+    rows of no slot or of a rank-0 slot are dropped. mf (1, 2, 4) is the
+    row-tile factor, by default picked from the host integers T and S. The
+    plan lives in buffers owned by (device, T, S, mf): it is valid until the
+    next lora_align of the same key."""
+    _lora_gpu_check(adapter_ids, "adapter_ids", torch.int32)
+    _lora_gpu_check(ranks, "ranks", torch.int32)
+    T, S = adapter_ids.numel(), ranks.numel()
+    if mf is None:
+        mf = _native().lora_pick_mf(T, S)
+    key = (adapter_ids.device.index, T, S, mf)
+    bufs = _lora_plans.get(key)
+    if bufs is None:
+        cap = lora_cap(T, S, mf)
+        bufs = _lora_plans[key] = (
+            torch.empty(cap, dtype=torch.int32, device=adapter_ids.device),
+            torch.empty(cap // (16 * mf), dtype=torch.int32, device=adapter_ids.device),
+        )
+    _native().lora_align(bufs[0], bufs[1], adapter_ids, ranks, mf)
+    return LoraPlan(bufs[0], bufs[1], mf, T)
+
+
+def lora_shrink_seg(
+    x: torch.Tensor, A: torch.Tensor, ranks: torch.Tensor,
+    adapter_ids: torch.Tensor, nseg: int, plan: Optional[LoraPlan] = None,
+    nsk: Optional[int] = None, out: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """GPU: the split-K partials of t in the plan's sorted order, fp32
+    [nsk, plan.cap, nseg*R] (`out` when given, else a view of the per-device
+    scratch, valid until the next call); lora_expand_seg sums them. Columns
+    at or above the slot's rank rounded up to 16 are not written. CPU:
+    reference.lora_shrink, t [T, nseg*R]."""
+    if not x.is_cuda:
+        return reference.lora_shrink(x, A, ranks, adapter_ids, nseg)
+    if plan is None:
+        raise ValueError("lora_shrink_seg on the GPU needs lora_align's plan")
+    plan.check(x, "x")
+    T, K, nR = x.shape[0], x.shape[1], A.shape[1]
+    if out is None:
+        if nsk is None:
+            nsk = _native().lora_pick_nsk(T, plan.mf, int(nseg), K)
+        n = nsk * plan.cap * nR
+        out = _lora_tpart.get(x.device, n)[:n].view(nsk, plan.cap, nR)
+    _native().lora_shrink_seg(
+        out, x, A, plan.sorted_rows, plan.tile_slot, ranks, int(nseg), plan.mf
+    )
+    return out
+
+
+def lora_expand_seg(
+    y: torch.Tensor, t: torch.Tensor, B: torch.Tensor, ranks: torch.Tensor,
+    scales: torch.Tensor, adapter_ids: torch.Tensor, seg_bounds,
+    plan: Optional[LoraPlan] = None,
+) -> torch.Tensor:
+    """lora_expand's result, in place on y, from lora_shrink_seg's t: the
+    partials are summed in ascending order, and rows in no tile of the plan
+    keep their bits. seg_bounds: multiples of 16. Returns y."""
+    seg_bounds = tuple(int(b) for b in seg_bounds)
+    N = y.shape[1]
+    if not (1 <= len(seg_bounds) <= 3) or seg_bounds[-1] != N:
+        raise ValueError(f"seg_bounds {seg_bounds} must be 1-3 ends, the last {N}")
+    if not y.is_cuda:
+        return reference.lora_expand(y, t, B, ranks, scales, adapter_ids, seg_bounds)
+    if plan is None:
+        raise ValueError("lora_expand_seg on the GPU needs lora_align's plan")
+    plan.check(y, "y")
+    _lora_gpu_check(scales, "scales", torch.float32)
+    starts = seg_bounds[:-1] + (N, N)  # a segment that is not there starts at N
+    _native().lora_expand_seg(
+        y, t, B, plan.sorted_rows, plan.tile_slot, ranks, scales,
+        len(seg_bounds), starts[0], starts[1], plan.mf,
+    )
+    return y
+
+
+def lora_seg_serves(stack: LoraStack, K: int) -> bool:
+    """The shapes lora_seg.hip serves: K in multiples of 64, segment bounds
+    in multiples of 16, at most three segments and LORA_SEG_MAX_SLOTS slots."""
+    return (
+        K % 64 == 0
+        and stack.nseg <= 3
+        and all(b % 16 == 0 for b in stack.seg_bounds)
+        and stack.ranks.numel() <= LORA_SEG_MAX_SLOTS
+    )
+
+
+def lora_plan(adapter_ids: torch.Tensor, ranks: torch.Tensor) -> Optional[LoraPlan]:
+    """The plan of one forward, shared by all its lora_add calls: None when
+    the batch is on the CPU or below LORA_SEG_MIN_T rows (vector kernels)."""
+    if not adapter_ids.is_cuda or adapter_ids.numel() < LORA_SEG_MIN_T:
+        return None
+    if ranks.numel() > LORA_SEG_MAX_SLOTS:
+        return None
+    return lora_align(adapter_ids, ranks)
+
+
 def lora_add(
-    y: torch.Tensor, x: torch.Tensor, stack: LoraStack, adapter_ids: torch.Tensor
+    y: torch.Tensor, x: torch.Tensor, stack: LoraStack, adapter_ids: torch.Tensor,
+    plan: Optional[LoraPlan] = None,
 ) -> torch.Tensor:
     """y += scale * B (A x) per row, in place on the projection's output y
-    = W x: lora_shrink then lora_expand over one projection's stack."""
+    = W x, over one projection's stack. From LORA_SEG_MIN_T rows on, on the
+    GPU and for the shapes lora_seg_serves, the segmented MFMA pair runs
+    (with `plan` when the caller already aligned these adapter_ids);
+    otherwise lora_shrink then lora_expand."""
+    if x.is_cuda and x.shape[0] >= LORA_SEG_MIN_T and lora_seg_serves(stack, x.shape[1]):
+        if plan is None:
+            plan = lora_align(adapter_ids, stack.ranks)
+        t = lora_shrink_seg(x, stack.A, stack.ranks, adapter_ids, stack.nseg, plan)
+        return lora_expand_seg(
+            y, t, stack.B, stack.ranks, stack.scales, adapter_ids,
+            stack.seg_bounds, plan,
+        )
     t = lora_shrink(x, stack.A, stack.ranks, adapter_ids, stack.nseg)
     return lora_expand(
         y, t, stack.B, stack.ranks, stack.scales, adapter_ids, stack.seg_bounds
@@ -1506,6 +1655,13 @@ __all__ = [
     "lora_shrink",
     "lora_expand",
     "lora_add",
+    "LoraPlan",
+    "lora_cap",
+    "lora_align",
+    "lora_shrink_seg",
+    "lora_expand_seg",
+    "lora_seg_serves",
+    "lora_plan",
     "MoePlan",
     "moe_check_shapes",
     "moe_pack_weights",

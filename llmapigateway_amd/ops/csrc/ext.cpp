@@ -25,6 +25,11 @@ hipError_t launch_sample(int64_t*, const float*, const float*, const float*, flo
 hipError_t launch_topk_topp_filter(float*, const float*, const int*, int, int, hipStream_t);
 hipError_t launch_lora_shrink(float*, const void*, const void*, const int*, const int*, int, int, int, int, int, hipStream_t);
 hipError_t launch_lora_expand(void*, const float*, const void*, const int*, const float*, const int*, int, int, int, int, int, int, int, hipStream_t);
+int lora_pick_mf(int, int);
+int lora_pick_nsk(int, int, int, int);
+hipError_t launch_lora_align(int*, int*, const int*, const int*, int, int, int, int, hipStream_t);
+hipError_t launch_lora_shrink_seg(float*, const void*, const void*, const int*, const int*, const int*, int, int, int, int, int, int, int, hipStream_t);
+hipError_t launch_lora_expand_seg(void*, const float*, const void*, const int*, const int*, const int*, const float*, int, int, int, int, int, int, int, int, int, hipStream_t);
 int moe_pick_mf(int, int, int);
 hipError_t launch_moe_route(int*, float*, const void*, const void*, int, int, int, int, hipStream_t);
 hipError_t launch_moe_align(int*, int*, const int*, int, int, int, int, hipStream_t);
@@ -651,6 +656,114 @@ void lora_expand(torch::Tensor y, torch::Tensor t, torch::Tensor B,
                                  current_stream()));
 }
 
+// ---- segmented multi-LoRA (lora_seg.hip) ----
+void check_i32(const torch::Tensor& t, const char* name);
+
+int64_t lora_pick_mf_py(int64_t T, int64_t S) {
+    return lora_pick_mf((int)T, (int)S);
+}
+
+int64_t lora_pick_nsk_py(int64_t T, int64_t mf, int64_t nseg, int64_t K) {
+    return lora_pick_nsk((int)T, (int)mf, (int)nseg, (int)K);
+}
+
+void lora_align(torch::Tensor sorted_rows, torch::Tensor tile_slot,
+                torch::Tensor adapter_ids, torch::Tensor ranks, int64_t mf) {
+    check_i32(sorted_rows, "sorted_rows");
+    check_i32(tile_slot, "tile_slot");
+    check_i32(adapter_ids, "adapter_ids");
+    check_i32(ranks, "ranks");
+    TORCH_CHECK(mf == 1 || mf == 2 || mf == 4, "mf must be 1, 2 or 4");
+    const int64_t T = adapter_ids.numel(), S = ranks.numel(), BM = 16 * mf;
+    const int64_t tiles = tile_slot.numel();
+    TORCH_CHECK(S >= 1 && S <= 64, "lora_align supports 1 <= S <= 64, got ", S);
+    TORCH_CHECK(T > 0 && tiles * BM >= T + S * (BM - 1) &&
+                sorted_rows.numel() == tiles * BM,
+                "sorted_rows [cap] / tile_slot [cap / BM] too small for ", T,
+                " rows of ", S, " slots");
+    CHECK_HIP(launch_lora_align(sorted_rows.data_ptr<int>(),
+                                tile_slot.data_ptr<int>(),
+                                adapter_ids.data_ptr<int>(),
+                                ranks.data_ptr<int>(), (int)T, (int)S, (int)mf,
+                                (int)tiles, current_stream()));
+}
+
+// the plan and the partial-t scratch [nsk, cap, nseg*R] of both kernels
+int64_t check_lora_seg(const torch::Tensor& tpart, const torch::Tensor& sorted_rows,
+                       const torch::Tensor& tile_slot, const torch::Tensor& ranks,
+                       int64_t S, int64_t R, int64_t nseg, int64_t mf) {
+    check_i32(sorted_rows, "sorted_rows");
+    check_i32(tile_slot, "tile_slot");
+    check_i32(ranks, "ranks");
+    TORCH_CHECK(mf == 1 || mf == 2 || mf == 4, "mf must be 1, 2 or 4");
+    TORCH_CHECK(nseg >= 1 && nseg <= 3, "nseg must be 1, 2 or 3");
+    TORCH_CHECK(R >= 8 && R <= 64 && R % 8 == 0,
+                "R must be a multiple of 8, at most 64");
+    TORCH_CHECK(S >= 1 && S <= 64 && ranks.numel() == S, "ranks must be int32 [S <= 64]");
+    const int64_t tiles = tile_slot.numel();
+    TORCH_CHECK(tiles >= 1 && sorted_rows.numel() == tiles * 16 * mf,
+                "sorted_rows must be [tiles * 16 * mf]");
+    TORCH_CHECK(tpart.is_cuda() && tpart.scalar_type() == torch::kFloat32 &&
+                tpart.is_contiguous() && tpart.dim() == 3 &&
+                tpart.size(0) >= 1 && tpart.size(1) == tiles * 16 * mf &&
+                tpart.size(2) == nseg * R &&
+                reinterpret_cast<uintptr_t>(tpart.data_ptr()) % 16 == 0,
+                "tpart must be fp32 [nsk, cap, nseg*R], 16-byte aligned");
+    return tiles;
+}
+
+void lora_shrink_seg(torch::Tensor tpart, torch::Tensor x, torch::Tensor A,
+                     torch::Tensor sorted_rows, torch::Tensor tile_slot,
+                     torch::Tensor ranks, int64_t nseg, int64_t mf) {
+    check_bf16(x, "x");
+    check_bf16(A, "A");
+    TORCH_CHECK(x.is_contiguous() && A.is_contiguous());
+    TORCH_CHECK(x.dim() == 2 && A.dim() == 3 && x.size(0) >= 1);
+    const int64_t K = x.size(1), S = A.size(0);
+    TORCH_CHECK(nseg >= 1 && A.size(2) == K && A.size(1) % nseg == 0,
+                "A must be [S, nseg*R, K]");
+    const int64_t R = A.size(1) / nseg;
+    TORCH_CHECK(K % 64 == 0, "K must be a multiple of 64");
+    const int64_t tiles =
+        check_lora_seg(tpart, sorted_rows, tile_slot, ranks, S, R, nseg, mf);
+    CHECK_HIP(launch_lora_shrink_seg(
+        tpart.data_ptr<float>(), x.data_ptr(), A.data_ptr(),
+        sorted_rows.data_ptr<int>(), tile_slot.data_ptr<int>(),
+        ranks.data_ptr<int>(), (int)S, (int)R, (int)nseg, (int)K, (int)mf,
+        (int)tiles, (int)tpart.size(0), current_stream()));
+}
+
+// b1/b2: first column of segment 1 / 2 (N where the segment does not exist)
+void lora_expand_seg(torch::Tensor y, torch::Tensor tpart, torch::Tensor B,
+                     torch::Tensor sorted_rows, torch::Tensor tile_slot,
+                     torch::Tensor ranks, torch::Tensor scales, int64_t nseg,
+                     int64_t b1, int64_t b2, int64_t mf) {
+    check_bf16(y, "y");
+    check_bf16(B, "B");
+    TORCH_CHECK(y.is_contiguous() && B.is_contiguous());
+    TORCH_CHECK(y.dim() == 2 && B.dim() == 3);
+    const int64_t N = y.size(1), S = B.size(0), R = B.size(2);
+    TORCH_CHECK(B.size(1) == N, "B must be [S, N, R]");
+    TORCH_CHECK(N % 16 == 0, "N must be a multiple of 16");
+    TORCH_CHECK(0 < b1 && b1 <= b2 && b2 <= N && b1 % 16 == 0 && b2 % 16 == 0,
+                "segment bounds must be ascending multiples of 16 within N");
+    TORCH_CHECK((nseg >= 2 || b1 == N) && (nseg >= 3 || b2 == N),
+                "a segment that does not exist starts at N");
+    TORCH_CHECK(scales.is_cuda() && scales.scalar_type() == torch::kFloat32 &&
+                scales.is_contiguous() && scales.numel() == S,
+                "scales must be fp32 [S]");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(y.data_ptr()) % 8 == 0,
+                "y must be 8-byte aligned");
+    const int64_t tiles =
+        check_lora_seg(tpart, sorted_rows, tile_slot, ranks, S, R, nseg, mf);
+    CHECK_HIP(launch_lora_expand_seg(
+        y.data_ptr(), tpart.data_ptr<float>(), B.data_ptr(),
+        sorted_rows.data_ptr<int>(), tile_slot.data_ptr<int>(),
+        ranks.data_ptr<int>(), scales.data_ptr<float>(), (int)S, (int)R,
+        (int)nseg, (int)N, (int)b1, (int)b2, (int)mf, (int)tiles,
+        (int)tpart.size(0), current_stream()));
+}
+
 // ---- mixture of experts (moe.hip) ----
 void check_moe_shape(int64_t E, int64_t k) {
     TORCH_CHECK(E >= 2 && E <= 64, "MoE kernels support 2 <= num_experts <= 64, got ", E);
@@ -849,6 +962,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("lora_expand", &lora_expand,
           "batched-gather LoRA expand y += scale[slot] * t @ B[slot].T in "
           "place, slot per row");
+    m.def("lora_pick_mf", &lora_pick_mf_py, "row-tile factor (BM = 16 mf) for T rows, S slots");
+    m.def("lora_pick_nsk", &lora_pick_nsk_py, "split-K of lora_shrink_seg for T, mf, nseg, K");
+    m.def("lora_align", &lora_align,
+          "stable counting sort of the rows by adapter slot, BM-padded");
+    m.def("lora_shrink_seg", &lora_shrink_seg,
+          "segmented MFMA LoRA shrink into split-K partials [nsk, cap, nseg*R]");
+    m.def("lora_expand_seg", &lora_expand_seg,
+          "segmented MFMA LoRA expand y += scale[slot] * t @ B[slot].T in place");
     m.def("rmsnorm", &rmsnorm, "RMSNorm (gfx950)");
     m.def("rmsnorm_residual", &rmsnorm_residual, "fused residual-add RMSNorm");
     m.def("rope_inplace", &rope_inplace, "rotate-half RoPE in place");

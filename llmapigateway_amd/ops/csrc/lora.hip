@@ -24,7 +24,10 @@
 //
 // These are the plain vector forms: a row's A and B traffic is served from
 // L2 when neighbouring rows share its adapter, but no tile is shared
-// between rows (docs/ROADMAP.md names the segmented MFMA form).
+// between rows. They serve decode batches and every shape; from
+// LLMAPI_LORA_SEG_MIN_T rows on, ops.lora_add takes the segmented MFMA
+// pair of lora_seg.hip instead (rows sorted by adapter, one adapter tile
+// shared by 16+ rows; profiles/r13_lora_segmented.md).
 
 #include "common.h"
 

@@ -30,6 +30,7 @@ sources = [
     os.path.join(CSRC, "gemm_w4.hip"),
     os.path.join(CSRC, "gemm_w4_m256.hip"),
     os.path.join(CSRC, "lora.hip"),
+    os.path.join(CSRC, "lora_seg.hip"),
     os.path.join(CSRC, "moe.hip"),
     os.path.join(CSRC, "moe_w4.hip"),
 ]
