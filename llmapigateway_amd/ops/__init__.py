@@ -1412,6 +1412,11 @@ MOE_MAX_TOPK = 8
 MOE_MAX_HIDDEN = 8192  # moe_route: four x rows in 64 KiB of dynamic LDS
 MOE_W4_GROUP = reference.MOE_W4_GROUP  # k of one group of the MXFP4 expert layout
 MOE_W4_RING_DEPTH = 4  # k groups; keep in sync with MW_D in moe_w4.hip
+# Pairs per expert on average (T*k / E) from which moe_mlp takes the 128-row
+# prefill tile (mf = 8, csrc/moe_prefill.hip) for bf16 experts;
+# LLMAPI_MOE_BIG_MIN_ROWS=n (read at call time) overrides it. Measured in
+# profiles/r14_moe_prefill.md.
+MOE_BIG_MIN_ROWS = 128
 
 
 def moe_check_shapes(E: int, k: int, H: int, inter: int, weight_dtype: str = "auto") -> None:
@@ -1451,6 +1456,22 @@ class MoePlan:
         self.cap = sorted_pairs.numel()
 
 
+def moe_big_serves(H: int, inter: int) -> bool:
+    """The shapes of the 128-row prefill tile: 128-column tiles of both
+    GEMMs. 2 * inter is a multiple of 128 for every inter moe_check_shapes
+    accepts, so only H decides."""
+    return H % 128 == 0
+
+
+def _moe_big_route(T: int, k: int, E: int, H: int, inter: int, quantised: bool) -> bool:
+    """moe_mlp's choice of the prefill tile, from host integers only (so it
+    is stable per graph bucket): bf16 experts, a shape the tile serves, and
+    at least MOE_BIG_MIN_ROWS pairs per expert on average."""
+    knob = os.environ.get("LLMAPI_MOE_BIG_MIN_ROWS")
+    min_rows = int(knob) if knob else MOE_BIG_MIN_ROWS
+    return not quantised and moe_big_serves(H, inter) and T * k >= min_rows * E
+
+
 def moe_pack_weights(w: torch.Tensor, gate_up: bool) -> torch.Tensor:
     """[E, N, K] expert stack -> the resident GPU layout (on w's device)."""
     return reference.moe_pack_weights(w, gate_up)
@@ -1475,8 +1496,9 @@ def moe_route(x: torch.Tensor, w_router: torch.Tensor, k: int):
 
 
 def moe_align(ids: torch.Tensor, E: int, mf: Optional[int] = None) -> MoePlan:
-    """GPU only: sort the pairs of ids [T, k] by expert. mf (1, 2, 4) is the
-    row-tile factor; by default picked from the host integers T*k/E."""
+    """GPU only: sort the pairs of ids [T, k] by expert. mf (1, 2, 4, or 8
+    for the prefill tile of bf16 experts) is the row-tile factor; by default
+    picked from the host integers T*k/E among 1, 2 and 4."""
     T, k = ids.shape
     if mf is None:
         mf = _native().moe_pick_mf(T, k, E)
@@ -1570,7 +1592,8 @@ def moe_mlp(
     (route, align, gate_up+swiglu, down, combine+norm), none of which reads
     device data on the host. ids/weights given: the router is skipped.
     s_gate_up / s_down given (both or neither): MXFP4 expert weights, see
-    moe_gate_up_swiglu."""
+    moe_gate_up_swiglu. A prefill batch of bf16 experts (_moe_big_route) runs
+    the two GEMMs on 128-row tiles, bit-identical to the 64-row ones."""
     if (s_gate_up is None) != (s_down is None):
         raise ValueError("moe_mlp takes s_gate_up and s_down together")
     if not x.is_cuda:
@@ -1585,7 +1608,9 @@ def moe_mlp(
         return reference.moe_combine_rmsnorm_residual(y_pair, residual, norm_w, eps, k)
     if ids is None:
         ids, weights = moe_route(x, w_router, k)
-    plan = moe_align(ids, w_gate_up.shape[0])
+    E, inter = w_gate_up.shape[0], w_gate_up.shape[2] * 8
+    big = _moe_big_route(x.shape[0], k, E, x.shape[1], inter, s_gate_up is not None)
+    plan = moe_align(ids, E, 8 if big else None)
     act = moe_gate_up_swiglu(x, ids, w_gate_up, plan, s_gate_up=s_gate_up)
     y_pair = moe_down(act, ids, weights, w_down, plan, s_down=s_down)
     return moe_combine_rmsnorm_residual(y_pair, residual, norm_w, eps, k)
@@ -1669,6 +1694,7 @@ __all__ = [
     "moe_pack_weights_mxfp4",
     "moe_unpack_weights_mxfp4",
     "moe_cap",
+    "moe_big_serves",
     "moe_route",
     "moe_align",
     "moe_gate_up_swiglu",

@@ -764,7 +764,7 @@ void lora_expand_seg(torch::Tensor y, torch::Tensor tpart, torch::Tensor B,
         (int)tpart.size(0), current_stream()));
 }
 
-// ---- mixture of experts (moe.hip) ----
+// ---- mixture of experts (moe.hip, moe_prefill.hip, moe_w4.hip) ----
 void check_moe_shape(int64_t E, int64_t k) {
     TORCH_CHECK(E >= 2 && E <= 64, "MoE kernels support 2 <= num_experts <= 64, got ", E);
     TORCH_CHECK(k >= 1 && k <= 8 && k <= E,
@@ -806,7 +806,7 @@ void moe_align(torch::Tensor sorted_pairs, torch::Tensor tile_expert,
     check_i32(sorted_pairs, "sorted_pairs");
     check_i32(tile_expert, "tile_expert");
     check_i32(ids, "ids");
-    TORCH_CHECK(mf == 1 || mf == 2 || mf == 4, "mf must be 1, 2 or 4");
+    TORCH_CHECK(mf == 1 || mf == 2 || mf == 4 || mf == 8, "mf must be 1, 2, 4 or 8");
     TORCH_CHECK(E >= 2 && E <= 64, "MoE kernels support 2 <= num_experts <= 64, got ", E);
     const int64_t P = ids.numel(), BM = 16 * mf, tiles = tile_expert.numel();
     TORCH_CHECK(P > 0 && tiles * BM >= P + E * (BM - 1) &&
@@ -831,7 +831,7 @@ void moe_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w,
     check_i32(sorted_pairs, "sorted_pairs");
     check_i32(tile_expert, "tile_expert");
     TORCH_CHECK(epi == 0 || epi == 1, "epi must be 0 (swiglu) or 1 (down)");
-    TORCH_CHECK(mf == 1 || mf == 2 || mf == 4, "mf must be 1, 2 or 4");
+    TORCH_CHECK(mf == 1 || mf == 2 || mf == 4 || mf == 8, "mf must be 1, 2, 4 or 8");
     TORCH_CHECK(out.is_contiguous() && a.is_contiguous() && w.is_contiguous() &&
                 out.dim() == 2 && a.dim() == 2);
     TORCH_CHECK(w.dim() == 5 && w.size(3) == 64 && w.size(4) == 8,
@@ -857,7 +857,8 @@ void moe_gemm(torch::Tensor out, torch::Tensor a, torch::Tensor w,
         TORCH_CHECK(a.size(0) == P / k, "x must be [T, H]");
         TORCH_CHECK(out.size(0) == cap && out.size(1) == N / 2, "act must be [cap, I]");
     } else {
-        TORCH_CHECK(N % 64 == 0, "hidden size must be a multiple of 64");
+        TORCH_CHECK(N % (mf == 8 ? 128 : 64) == 0, "hidden size must be a multiple of ",
+                    mf == 8 ? 128 : 64, " at mf = ", mf);
         TORCH_CHECK(a.size(0) == cap, "act must be [cap, I]");
         TORCH_CHECK(out.size(0) == P && out.size(1) == N, "y_pair must be [T*k, H]");
     }

@@ -18,6 +18,9 @@
 //                     EPI_SWIGLU writes act [cap, I] in sorted order;
 //                     EPI_DOWN scales by the routing weight and scatters
 //                     the row to y_pair [T·k, H] in pair order.
+//   moe_gemm_big<EPI> the same GEMM for prefill row counts (mf = 8, a
+//                     128 x 128 tile with both operands shared through LDS),
+//                     bit-identical to moe_gemm<4>: moe_prefill.hip.
 //   moe_combine_norm  residual += sum_j y_pair[t·k + j] (fixed j order,
 //                     fp32), then the RMSNorm of the new residual.
 //
@@ -471,6 +474,12 @@ hipError_t launch_gemm_epi(int mf, dim3 grid, hipStream_t stream, bf16* out,
 
 }  // namespace
 
+// moe_prefill.hip: the 128-row tile
+extern "C" hipError_t launch_moe_gemm_big(
+    void* out, const void* a, const void* w, const int* sorted_pairs,
+    const int* tile_expert, const float* rweights, int epi, int max_tiles,
+    int N, int K, int k, hipStream_t stream);
+
 // rows per expert on average decide the row tile: a decode batch does not
 // pad every expert to 64 rows, a prefill does not run 16-row tiles. From
 // host integers only, so it is stable per graph bucket.
@@ -497,7 +506,7 @@ extern "C" hipError_t launch_moe_route(
 extern "C" hipError_t launch_moe_align(
     int* sorted_pairs, int* tile_expert, const int* ids, int P, int E, int mf,
     int max_tiles, hipStream_t stream) {
-    if (mf != 1 && mf != 2 && mf != 4) return hipErrorInvalidValue;
+    if (mf != 1 && mf != 2 && mf != 4 && mf != 8) return hipErrorInvalidValue;
     const int BM = 16 * mf;
     if (P <= 0 || E < 2 || E > MOE_MAX_E) return hipErrorInvalidValue;
     if ((long)max_tiles * BM < (long)P + (long)E * (BM - 1))
@@ -510,12 +519,16 @@ extern "C" hipError_t launch_moe_align(
 
 // epi 0: act [cap, N/2] = swiglu(gather(x) · w[e]^T), N = 2I, K = H
 // epi 1: y_pair [P, N] = rweights · (act · w[e]^T),   N = H,  K = I
+// mf = 8 is moe_gemm_big (moe_prefill.hip): N % 128 == 0 for both epilogues
 extern "C" hipError_t launch_moe_gemm(
     void* out, const void* a, const void* w, const int* sorted_pairs,
     const int* tile_expert, const float* rweights, int epi, int mf,
     int max_tiles, int N, int K, int k, hipStream_t stream) {
     if (max_tiles <= 0 || k < 1 || K <= 0 || K % MG_BK != 0)
         return hipErrorInvalidValue;
+    if (mf == 8)
+        return launch_moe_gemm_big(out, a, w, sorted_pairs, tile_expert,
+                                   rweights, epi, max_tiles, N, K, k, stream);
     if (epi == EPI_SWIGLU) {
         if (N <= 0 || N % 128 != 0) return hipErrorInvalidValue;
         return launch_gemm_epi<EPI_SWIGLU>(

@@ -32,6 +32,7 @@ sources = [
     os.path.join(CSRC, "lora.hip"),
     os.path.join(CSRC, "lora_seg.hip"),
     os.path.join(CSRC, "moe.hip"),
+    os.path.join(CSRC, "moe_prefill.hip"),
     os.path.join(CSRC, "moe_w4.hip"),
 ]
 

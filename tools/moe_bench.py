@@ -14,6 +14,11 @@ with uniform-random routing, beside two baselines at the same T:
 
 The last column times moe_align alone (warm, the sort of the T*k pairs).
 
+Where moe_mlp takes the 128-row prefill tile (csrc/moe_prefill.hip; the mf
+column shows the tile actually used), the same call is also timed with
+LLMAPI_MOE_BIG_MIN_ROWS set high, which forces the 64-row kernels, in the same
+alternating rounds.
+
 --weight-dtype=auto,mxfp4 also times moe_mlp on the MXFP4 quantisation of the
 same expert weights (csrc/moe_w4.hip) in the same alternating rounds and
 prints a second line per T.
@@ -23,7 +28,7 @@ weights (each layer's experts are 2.8 GB, far beyond the 256 MB L3), routes
 alternate, three rounds each; the median round is reported with the min-max
 of the three. Run on the GPU box:
 
-    python tools/moe_bench.py [--ts=16,64,256,4096] [--weight-dtype=auto,mxfp4]
+    python tools/moe_bench.py [--ts=16,64,256,512,1024,2048,4096] [--weight-dtype=auto,mxfp4]
 """
 
 import os
@@ -37,7 +42,7 @@ import torch
 from llmapigateway_amd import ops
 
 H, INTER, E, K = 4096, 14336, 8, 2
-TS = (16, 64, 256, 4096)
+TS = (16, 64, 256, 512, 1024, 2048, 4096)
 MOE_LAYERS = 2    # 5.6 GB of expert weights per form
 DENSE_LAYERS = 5  # 1.7 GB of dense MLP weights
 
@@ -115,8 +120,9 @@ def main():
     ]
     torch.cuda.empty_cache()
 
-    print("T, mf, moe_mlp us, (a) dense 8b MLP us, (b) host-synced expert loop us, "
-          "moe/(a), moe/(b), expert weight bytes / moe_mlp time GB/s, moe_align alone us")
+    print("T, mf, moe_mlp us, moe_mlp on the 64-row kernels us, (a) dense 8b MLP us, "
+          "(b) host-synced expert loop us, moe/(a), moe/(b), expert weight bytes / "
+          "moe_mlp time GB/s, moe_align alone us")
     for T in ts:
         x = (torch.randn(T, H, device=dev) * 0.5).bfloat16()
         res = torch.zeros(T, H, dtype=torch.bfloat16, device=dev)
@@ -128,6 +134,13 @@ def main():
             j = i % MOE_LAYERS
             return ops.moe_mlp(x, router, gu_pack[j], dn_pack[j], K, res, norm_w,
                                1e-5, ids=ids, weights=wts)
+
+        def moe_old(i):
+            os.environ["LLMAPI_MOE_BIG_MIN_ROWS"] = str(10**9)
+            try:
+                return moe(i)
+            finally:
+                del os.environ["LLMAPI_MOE_BIG_MIN_ROWS"]
 
         def moe_w4(i):
             j = i % MOE_LAYERS
@@ -166,15 +179,18 @@ def main():
             return ops.moe_align(ids, E)
 
         # windows of 0.1-0.3 s per round
-        iters = 300 if T <= 256 else 40
+        iters = 300 if T <= 256 else 100 if T <= 1024 else 40
+        big = ops._moe_big_route(T, K, E, H, INTER, False)
         m, a, b, *q = rounds(
-            [moe, dense, loop] + ([moe_w4] if w4 else []), iters
+            [moe, dense, loop] + ([moe_old] if big else []) + ([moe_w4] if w4 else []),
+            iters,
         )
+        old = fmt(q.pop(0)) if big else "-"
         (al,) = rounds([align], 300)
         used = len(torch.unique(ids)) * 3 * H * INTER * 2  # bytes of experts hit
-        mf = ops._native().moe_pick_mf(T, K, E)
+        mf = 8 if big else ops._native().moe_pick_mf(T, K, E)
         print(
-            f"{T}, {mf}, {fmt(m)}, {fmt(a)}, {fmt(b)}, {m[0] / a[0]:.2f}, "
+            f"{T}, {mf}, {fmt(m)}, {old}, {fmt(a)}, {fmt(b)}, {m[0] / a[0]:.2f}, "
             f"{m[0] / b[0]:.2f}, {used / m[0] / 1e3:.0f}, {fmt(al)}",
             flush=True,
         )
