@@ -10,7 +10,7 @@ PyTorch. CPU tensors use ops.reference (fp32 semantics contract).
 from __future__ import annotations
 
 import os
-from typing import Optional, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 # Enable the pre-tuned hipBLASLt/rocBLAS GEMM selections for gfx950 (3.2x on
 # the decode lm_head GEMM). torch appends the device ordinal before ".csv",
@@ -716,6 +716,146 @@ def _w8_gpu_check(x: torch.Tensor) -> None:
         )
 
 
+class _Quant(NamedTuple):
+    """What differs between the quantised weight formats on the linear
+    routes below. (q_frag, w2) is the fragment-major twin: w2 is the fp32
+    channel scale of fp8, the e8m0 block-scale twin of MXFP4. The functions
+    are lambdas over module-level names, so those are looked up when a route
+    runs, not when the description is built."""
+    gemm: str                # native streaming kernel (M <= 256)
+    gemm_m256: str           # native macro-tile kernel
+    n_of: Callable           # q_frag -> N
+    nsk: Callable            # (N, K) -> split-K factor of the streaming kernel
+    macro_config: Callable   # (M, N, K) -> {"nf", "nsk"} or None, knob applied
+    macro_default: Callable  # (M, N, K) -> {"nf", "nsk"} where nothing was measured
+    dequant: Callable        # (q_frag, w2) -> row-major bf16 [N, K]
+    reference: Callable      # (x, q_frag, w2) -> y, on the CPU
+
+
+def _m256_table_config(table: dict, ms: tuple, M: int, N: int, K: int) -> Optional[dict]:
+    """Look (M, N, K) up in a measured macro-tile dispatch table (N, K) ->
+    {measured M: (nf, nsk) or None}. Only the measured shapes have entries.
+    A measured M takes its own cell; an M between two measured batch sizes
+    takes the upper one's configuration (the kernel runs the same wave count
+    there), and only where the macro kernel won at BOTH ends; below the
+    smallest measured M nothing is assumed."""
+    row = table.get((N, K))
+    if row is None or not (ms[0] <= M <= ms[-1]):
+        return None
+    hi = next(i for i, m in enumerate(ms) if m >= M)
+    cell = row[ms[hi]]
+    if cell is None or (M != ms[hi] and row[ms[hi - 1]] is None):
+        return None
+    return {"nf": cell[0], "nsk": cell[1]}
+
+
+def _macro_knob_config(knob: str, config: Callable, M: int, N: int, K: int) -> Optional[dict]:
+    """config(M, N, K) where the env knob (read at call time) is set to an
+    m with m <= M <= 256, else None."""
+    v = os.environ.get(knob)
+    if not v or not (int(v) <= M <= _W8_MAX_M):
+        return None
+    return config(M, N, K)
+
+
+def _quant_gemm_m256(fmt: _Quant, x, q_frag, w2, nf, nsk) -> torch.Tensor:
+    M, K = x.shape
+    N = fmt.n_of(q_frag)
+    cfg = fmt.macro_default(M, N, K)
+    if nf is None:
+        nf = cfg["nf"]
+    if nsk is None:
+        nsk = cfg["nsk"] if nf == cfg["nf"] else _m256_nsk(N, K, nf)
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    ws = _slabs.get(x.device, nsk * M * N) if nsk > 1 else None
+    getattr(_native(), fmt.gemm_m256)(y, x, q_frag, w2, ws, nsk, nf)
+    return y
+
+
+def _quant_gemm_m256_norm(fmt: _Quant, x, q_frag, w2, residual, norm_w, eps, nf, nsk):
+    if nsk < 2:
+        raise ValueError("fused reduce+norm needs split-K slabs (nsk > 1)")
+    return _splitk_norm(
+        lambda y, ws, *tail: getattr(_native(), fmt.gemm_m256)(
+            y, x, q_frag, w2, ws, nsk, nf, *tail
+        ),
+        x, fmt.n_of(q_frag), nsk, residual, norm_w, eps,
+    )
+
+
+def _quant_linear(fmt: _Quant, x, q_frag, w2, nsk) -> torch.Tensor:
+    if not x.is_cuda:
+        return fmt.reference(x, q_frag, w2)
+    _w8_gpu_check(x)
+    M, K = x.shape
+    N = fmt.n_of(q_frag)
+    if M > _W8_MAX_M:
+        return torch.nn.functional.linear(x, fmt.dequant(q_frag, w2))
+    if nsk is None:
+        macro = fmt.macro_config(M, N, K)
+        if macro is not None:
+            return _quant_gemm_m256(fmt, x, q_frag, w2, **macro)
+        nsk = fmt.nsk(N, K)
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    ws = _slabs.get(x.device, nsk * M * N) if nsk > 1 else None
+    getattr(_native(), fmt.gemm)(y, x, q_frag, w2, ws, nsk)
+    return y
+
+
+def _quant_linear_norm(fmt: _Quant, x, q_frag, w2, residual, norm_w, eps, nsk):
+    if x.is_cuda and not os.environ.get("LLMAPI_NO_DECODE_FUSION"):
+        _w8_gpu_check(x)
+        M, K = x.shape
+        N = fmt.n_of(q_frag)
+        fusable = _reduce_norm_covers(N) and residual.is_contiguous()
+        macro = fmt.macro_config(M, N, K) if nsk is None else None
+        if macro is not None:
+            if macro["nsk"] > 1 and fusable:
+                return _quant_gemm_m256_norm(
+                    fmt, x, q_frag, w2, residual, norm_w, eps, **macro
+                )
+            return rmsnorm_residual(
+                _quant_gemm_m256(fmt, x, q_frag, w2, **macro), residual, norm_w, eps
+            )
+        k = fmt.nsk(N, K) if nsk is None else nsk
+        if M <= _W8_MAX_M and k > 1 and fusable:
+            return _splitk_norm(
+                lambda y, ws, *tail: getattr(_native(), fmt.gemm)(
+                    y, x, q_frag, w2, ws, k, *tail
+                ),
+                x, N, k, residual, norm_w, eps,
+            )
+    return rmsnorm_residual(
+        _quant_linear(fmt, x, q_frag, w2, nsk), residual, norm_w, eps
+    )
+
+
+_W8 = _Quant(
+    gemm="gemm_w8",
+    gemm_m256="gemm_w8_m256",
+    n_of=lambda q_frag: q_frag.shape[1] * 16,
+    nsk=lambda N, K: _w8_nsk(N, K),
+    macro_config=lambda M, N, K: _w8_macro_config(M, N, K),
+    macro_default=lambda M, N, K: _w8_m256_default(M, N, K),
+    dequant=lambda q_frag, scale: dequant_w8(q_frag, scale),
+    reference=lambda x, q_frag, scale: reference.linear_w8(
+        x, reference.unswizzle_weight_frag_fp8(q_frag), scale
+    ),
+)
+_W4 = _Quant(
+    gemm="gemm_w4",
+    gemm_m256="gemm_w4_m256",
+    n_of=lambda q_frag: q_frag.shape[1] * 16,
+    nsk=lambda N, K: _w4_nsk(N, K),
+    macro_config=lambda M, N, K: _w4_macro_config(M, N, K),
+    macro_default=lambda M, N, K: _w4_m256_default(M, N, K),
+    dequant=lambda q_frag, s_frag: dequant_w4(q_frag, s_frag),
+    reference=lambda x, q_frag, s_frag: reference.linear_w4(
+        x, *reference.unswizzle_weight_frag_mxfp4(q_frag, s_frag)
+    ),
+)
+
+
 def _w8_m256_default(M: int, N: int, K: int) -> dict:
     """nf and nsk of the macro-tile fp8 kernel where nothing was measured:
     nf by gemm_m256's rule (4 when N % 128 != 0), nsk from _m256_nsk."""
@@ -781,29 +921,16 @@ _W8_M256_MS = (64, 128, 256)  # the batch sizes the sweep measured
 def _w8_m256_config(M: int, N: int, K: int) -> Optional[dict]:
     """Measured dispatch table of the macro-tile fp8 kernel
     (csrc/gemm_w8_m256.hip) against the streaming fp8 kernel. Returns
-    {"nf", "nsk"}, or None to keep the streaming kernel. Only the measured
-    shapes have entries. A measured M takes its own cell; an M between two
-    measured batch sizes takes the upper one's configuration (the kernel
-    runs the same wave count there), and only where the macro kernel won at
-    BOTH ends; below the smallest measured M nothing is assumed."""
-    row = _W8_M256_TABLE.get((N, K))
-    if row is None or not (_W8_M256_MS[0] <= M <= _W8_M256_MS[-1]):
-        return None
-    hi = next(i for i, m in enumerate(_W8_M256_MS) if m >= M)
-    cell = row[_W8_M256_MS[hi]]
-    if cell is None or (M != _W8_M256_MS[hi] and row[_W8_M256_MS[hi - 1]] is None):
-        return None
-    return {"nf": cell[0], "nsk": cell[1]}
+    {"nf", "nsk"}, or None to keep the streaming kernel; the lookup rule is
+    _m256_table_config's."""
+    return _m256_table_config(_W8_M256_TABLE, _W8_M256_MS, M, N, K)
 
 
 def _w8_macro_config(M: int, N: int, K: int) -> Optional[dict]:
     """The macro-tile route of linear_w8 for this call, or None. Opt-in:
     LLMAPI_W8_MACRO_MIN_M=m (read at call time) sends m <= M <= 256 to
     gemm_w8_m256 wherever the measured table has an entry."""
-    knob = os.environ.get("LLMAPI_W8_MACRO_MIN_M")
-    if not knob or not (int(knob) <= M <= _W8_MAX_M):
-        return None
-    return _w8_m256_config(M, N, K)
+    return _macro_knob_config("LLMAPI_W8_MACRO_MIN_M", _w8_m256_config, M, N, K)
 
 
 def gemm_w8_m256(
@@ -811,20 +938,11 @@ def gemm_w8_m256(
     nf: Optional[int] = None, nsk: Optional[int] = None,
 ) -> torch.Tensor:
     """y = x @ (scale * q).T on the macro-tile W8A16 kernel
-    (csrc/gemm_w8_m256.hip): the structure of the register-staged gemm_m256
-    with the fp8 twin converted once per workgroup into the LDS tile.
-    M <= 256; nf in {4, 8} is the column-tile width in 16-col fragments."""
-    M, K = x.shape
-    N = q_frag.shape[1] * 16
-    cfg = _w8_m256_default(M, N, K)
-    if nf is None:
-        nf = cfg["nf"]
-    if nsk is None:
-        nsk = cfg["nsk"] if nf == cfg["nf"] else _m256_nsk(N, K, nf)
-    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    ws = _slabs.get(x.device, nsk * M * N) if nsk > 1 else None
-    _native().gemm_w8_m256(y, x, q_frag, scale, ws, nsk, nf)
-    return y
+    (csrc/gemm_w8_m256.hip): the register-staged pipeline of
+    csrc/gemm_macro.h with the fp8 twin converted once per workgroup into
+    the LDS tile. M <= 256; nf in {4, 8} is the column-tile width in 16-col
+    fragments."""
+    return _quant_gemm_m256(_W8, x, q_frag, scale, nf, nsk)
 
 
 def gemm_w8_m256_rmsnorm_residual(
@@ -836,14 +954,7 @@ def gemm_w8_m256_rmsnorm_residual(
     with the residual add and the norm fused into the split-K slab
     reduction; residual is updated in place, bit-identical to the unfused
     pair. Needs nsk > 1."""
-    if nsk < 2:
-        raise ValueError("fused reduce+norm needs split-K slabs (nsk > 1)")
-    return _splitk_norm(
-        lambda y, ws, *tail: _native().gemm_w8_m256(
-            y, x, q_frag, scale, ws, nsk, nf, *tail
-        ),
-        x, q_frag.shape[1] * 16, nsk, residual, norm_w, eps,
-    )
+    return _quant_gemm_m256_norm(_W8, x, q_frag, scale, residual, norm_w, eps, nf, nsk)
 
 
 def linear_w8(
@@ -857,24 +968,7 @@ def linear_w8(
     library GEMM. With LLMAPI_W8_MACRO_MIN_M=m set and no explicit nsk,
     m <= M <= 256 runs the macro-tile kernel (csrc/gemm_w8_m256.hip) for
     the shapes _w8_m256_config lists. CPU: the reference."""
-    if not x.is_cuda:
-        return reference.linear_w8(
-            x, reference.unswizzle_weight_frag_fp8(q_frag), scale
-        )
-    _w8_gpu_check(x)
-    M, K = x.shape
-    N = q_frag.shape[1] * 16
-    if M > _W8_MAX_M:
-        return torch.nn.functional.linear(x, dequant_w8(q_frag, scale))
-    if nsk is None:
-        macro = _w8_macro_config(M, N, K)
-        if macro is not None:
-            return gemm_w8_m256(x, q_frag, scale, **macro)
-        nsk = _w8_nsk(N, K)
-    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    ws = _slabs.get(x.device, nsk * M * N) if nsk > 1 else None
-    _native().gemm_w8(y, x, q_frag, scale, ws, nsk)
-    return y
+    return _quant_linear(_W8, x, q_frag, scale, nsk)
 
 
 def linear_w8_rmsnorm_residual(
@@ -889,37 +983,7 @@ def linear_w8_rmsnorm_residual(
     runs (LLMAPI_NO_DECODE_FUSION=1 forces it). The same holds on the
     macro-tile route (LLMAPI_W8_MACRO_MIN_M, see linear_w8) with that
     kernel's nsk."""
-    if x.is_cuda and not os.environ.get("LLMAPI_NO_DECODE_FUSION"):
-        _w8_gpu_check(x)
-        M, K = x.shape
-        N = q_frag.shape[1] * 16
-        macro = _w8_macro_config(M, N, K) if nsk is None else None
-        if macro is not None:
-            if (
-                macro["nsk"] > 1
-                and _reduce_norm_covers(N)
-                and residual.is_contiguous()
-            ):
-                return gemm_w8_m256_rmsnorm_residual(
-                    x, q_frag, scale, residual, norm_w, eps, **macro
-                )
-            return rmsnorm_residual(
-                gemm_w8_m256(x, q_frag, scale, **macro), residual, norm_w, eps
-            )
-        k = _w8_nsk(N, K) if nsk is None else nsk
-        if (
-            M <= _W8_MAX_M
-            and k > 1
-            and _reduce_norm_covers(N)
-            and residual.is_contiguous()
-        ):
-            return _splitk_norm(
-                lambda y, ws, *tail: _native().gemm_w8(
-                    y, x, q_frag, scale, ws, k, *tail
-                ),
-                x, N, k, residual, norm_w, eps,
-            )
-    return rmsnorm_residual(linear_w8(x, q_frag, scale, nsk), residual, norm_w, eps)
+    return _quant_linear_norm(_W8, x, q_frag, scale, residual, norm_w, eps, nsk)
 
 
 # ---- MXFP4 weights: W4A16 decode GEMM (csrc/gemm_w4.hip) ----
@@ -1005,29 +1069,16 @@ _W4_M256_MS = (64, 128, 256)  # the batch sizes the sweep measured
 def _w4_m256_config(M: int, N: int, K: int) -> Optional[dict]:
     """Measured dispatch table of the macro-tile MXFP4 kernel
     (csrc/gemm_w4_m256.hip) against the streaming MXFP4 kernel. Returns
-    {"nf", "nsk"}, or None to keep the streaming kernel. The lookup is
-    _w8_m256_config's: only the measured shapes have entries; a measured M
-    takes its own cell; an M between two measured batch sizes takes the
-    upper one's configuration, and only where the macro kernel won at BOTH
-    ends; below the smallest measured M nothing is assumed."""
-    row = _W4_M256_TABLE.get((N, K))
-    if row is None or not (_W4_M256_MS[0] <= M <= _W4_M256_MS[-1]):
-        return None
-    hi = next(i for i, m in enumerate(_W4_M256_MS) if m >= M)
-    cell = row[_W4_M256_MS[hi]]
-    if cell is None or (M != _W4_M256_MS[hi] and row[_W4_M256_MS[hi - 1]] is None):
-        return None
-    return {"nf": cell[0], "nsk": cell[1]}
+    {"nf", "nsk"}, or None to keep the streaming kernel; the lookup rule is
+    _m256_table_config's."""
+    return _m256_table_config(_W4_M256_TABLE, _W4_M256_MS, M, N, K)
 
 
 def _w4_macro_config(M: int, N: int, K: int) -> Optional[dict]:
     """The macro-tile route of linear_w4 for this call, or None. Opt-in:
     LLMAPI_W4_MACRO_MIN_M=m (read at call time) sends m <= M <= 256 to
     gemm_w4_m256 wherever the measured table has an entry."""
-    knob = os.environ.get("LLMAPI_W4_MACRO_MIN_M")
-    if not knob or not (int(knob) <= M <= _W8_MAX_M):
-        return None
-    return _w4_m256_config(M, N, K)
+    return _macro_knob_config("LLMAPI_W4_MACRO_MIN_M", _w4_m256_config, M, N, K)
 
 
 def gemm_w4_m256(
@@ -1035,20 +1086,11 @@ def gemm_w4_m256(
     nf: Optional[int] = None, nsk: Optional[int] = None,
 ) -> torch.Tensor:
     """y = x @ dequant(q, s).T on the macro-tile W4A16 kernel
-    (csrc/gemm_w4_m256.hip): the structure of gemm_w8_m256 with the MXFP4
-    twin converted once per workgroup into the LDS tile. M <= 256; nf in
-    {4, 8} is the column-tile width in 16-col fragments."""
-    M, K = x.shape
-    N = q_frag.shape[1] * 16
-    cfg = _w4_m256_default(M, N, K)
-    if nf is None:
-        nf = cfg["nf"]
-    if nsk is None:
-        nsk = cfg["nsk"] if nf == cfg["nf"] else _m256_nsk(N, K, nf)
-    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    ws = _slabs.get(x.device, nsk * M * N) if nsk > 1 else None
-    _native().gemm_w4_m256(y, x, q_frag, s_frag, ws, nsk, nf)
-    return y
+    (csrc/gemm_w4_m256.hip): the register-staged pipeline of
+    csrc/gemm_macro.h with the MXFP4 twin converted once per workgroup into
+    the LDS tile. M <= 256; nf in {4, 8} is the column-tile width in 16-col
+    fragments."""
+    return _quant_gemm_m256(_W4, x, q_frag, s_frag, nf, nsk)
 
 
 def gemm_w4_m256_rmsnorm_residual(
@@ -1060,14 +1102,7 @@ def gemm_w4_m256_rmsnorm_residual(
     with the residual add and the norm fused into the split-K slab
     reduction; residual is updated in place, bit-identical to the unfused
     pair. Needs nsk > 1."""
-    if nsk < 2:
-        raise ValueError("fused reduce+norm needs split-K slabs (nsk > 1)")
-    return _splitk_norm(
-        lambda y, ws, *tail: _native().gemm_w4_m256(
-            y, x, q_frag, s_frag, ws, nsk, nf, *tail
-        ),
-        x, q_frag.shape[1] * 16, nsk, residual, norm_w, eps,
-    )
+    return _quant_gemm_m256_norm(_W4, x, q_frag, s_frag, residual, norm_w, eps, nf, nsk)
 
 
 def linear_w4(
@@ -1082,24 +1117,7 @@ def linear_w4(
     explicit nsk, m <= M <= 256 runs the macro-tile kernel
     (csrc/gemm_w4_m256.hip) for the shapes _w4_m256_config lists. CPU: the
     reference."""
-    if not x.is_cuda:
-        return reference.linear_w4(
-            x, *reference.unswizzle_weight_frag_mxfp4(q_frag, s_frag)
-        )
-    _w8_gpu_check(x)
-    M, K = x.shape
-    N = q_frag.shape[1] * 16
-    if M > _W8_MAX_M:
-        return torch.nn.functional.linear(x, dequant_w4(q_frag, s_frag))
-    if nsk is None:
-        macro = _w4_macro_config(M, N, K)
-        if macro is not None:
-            return gemm_w4_m256(x, q_frag, s_frag, **macro)
-        nsk = _w4_nsk(N, K)
-    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    ws = _slabs.get(x.device, nsk * M * N) if nsk > 1 else None
-    _native().gemm_w4(y, x, q_frag, s_frag, ws, nsk)
-    return y
+    return _quant_linear(_W4, x, q_frag, s_frag, nsk)
 
 
 def linear_w4_rmsnorm_residual(
@@ -1114,37 +1132,7 @@ def linear_w4_rmsnorm_residual(
     runs (LLMAPI_NO_DECODE_FUSION=1 forces it). The same holds on the
     macro-tile route (LLMAPI_W4_MACRO_MIN_M, see linear_w4) with that
     kernel's nsk."""
-    if x.is_cuda and not os.environ.get("LLMAPI_NO_DECODE_FUSION"):
-        _w8_gpu_check(x)
-        M, K = x.shape
-        N = q_frag.shape[1] * 16
-        macro = _w4_macro_config(M, N, K) if nsk is None else None
-        if macro is not None:
-            if (
-                macro["nsk"] > 1
-                and _reduce_norm_covers(N)
-                and residual.is_contiguous()
-            ):
-                return gemm_w4_m256_rmsnorm_residual(
-                    x, q_frag, s_frag, residual, norm_w, eps, **macro
-                )
-            return rmsnorm_residual(
-                gemm_w4_m256(x, q_frag, s_frag, **macro), residual, norm_w, eps
-            )
-        k = _w4_nsk(N, K) if nsk is None else nsk
-        if (
-            M <= _W8_MAX_M
-            and k > 1
-            and _reduce_norm_covers(N)
-            and residual.is_contiguous()
-        ):
-            return _splitk_norm(
-                lambda y, ws, *tail: _native().gemm_w4(
-                    y, x, q_frag, s_frag, ws, k, *tail
-                ),
-                x, N, k, residual, norm_w, eps,
-            )
-    return rmsnorm_residual(linear_w4(x, q_frag, s_frag, nsk), residual, norm_w, eps)
+    return _quant_linear_norm(_W4, x, q_frag, s_frag, residual, norm_w, eps, nsk)
 
 
 # ---- multi-LoRA: batched-gather adapter kernels (csrc/lora.hip) ----

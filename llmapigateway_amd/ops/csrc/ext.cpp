@@ -463,19 +463,25 @@ void gemm_w8(torch::Tensor y, torch::Tensor x, torch::Tensor q_frag,
                              current_stream()));
 }
 
-void gemm_w8_m256(torch::Tensor y, torch::Tensor x, torch::Tensor q_frag,
-                  torch::Tensor scale, c10::optional<torch::Tensor> workspace,
-                  int64_t nsk, int64_t nf,
-                  c10::optional<torch::Tensor> residual,
-                  c10::optional<torch::Tensor> norm_weight, double eps,
-                  c10::optional<torch::Tensor> out) {
+// The macro-tile quantised bindings differ in the weight check and the
+// launcher only: q_frag with its second operand w2 (fp8: channel scales,
+// MXFP4: block scales).
+template <class Launch>
+void gemm_quant_m256(const char* op,
+                     int (*check_w)(const torch::Tensor&, const torch::Tensor&, int),
+                     Launch launch, torch::Tensor& y, const torch::Tensor& x,
+                     const torch::Tensor& q_frag, const torch::Tensor& w2,
+                     const c10::optional<torch::Tensor>& workspace, int64_t nsk,
+                     int64_t nf, const c10::optional<torch::Tensor>& residual,
+                     const c10::optional<torch::Tensor>& norm_weight, double eps,
+                     const c10::optional<torch::Tensor>& out) {
     check_bf16(x, "x");
     check_bf16(y, "y");
     TORCH_CHECK(x.is_contiguous() && y.is_contiguous());
     TORCH_CHECK(x.dim() == 2 && y.dim() == 2);
     const int M = x.size(0), K = x.size(1);
-    TORCH_CHECK(M >= 1 && M <= 256, "gemm_w8_m256 covers 1 <= M <= 256");
-    const int N = check_w8(q_frag, scale, K);
+    TORCH_CHECK(M >= 1 && M <= 256, op, " covers 1 <= M <= 256");
+    const int N = check_w(q_frag, w2, K);
     TORCH_CHECK(y.size(0) == M && y.size(1) == N);
     TORCH_CHECK(nf == 4 || nf == 8, "nf must be 4 or 8");
     TORCH_CHECK(N % (16 * nf) == 0, "N must be a multiple of 16*nf");
@@ -484,11 +490,24 @@ void gemm_w8_m256(torch::Tensor y, torch::Tensor x, torch::Tensor q_frag,
     float* ws = workspace_ptr(workspace, nsk * (int64_t)M * N);
     TORCH_CHECK(nsk == 1 || ws != nullptr, "split-K needs a workspace");
     const NormTail t = norm_tail(residual, norm_weight, out, M, N, nsk, ws);
-    CHECK_HIP(launch_gemm_w8_m256(y.data_ptr(), ws, x.data_ptr(),
-                                  q_frag.data_ptr(), scale.data_ptr<float>(),
-                                  M, N, K, (int)nsk, (int)nf, t.residual,
-                                  t.norm_weight, (float)eps, t.out,
-                                  current_stream()));
+    CHECK_HIP(launch(y.data_ptr(), ws, x.data_ptr(), q_frag.data_ptr(),
+                     w2.data_ptr(), M, N, K, (int)nsk, (int)nf, t.residual,
+                     t.norm_weight, (float)eps, t.out, current_stream()));
+}
+
+void gemm_w8_m256(torch::Tensor y, torch::Tensor x, torch::Tensor q_frag,
+                  torch::Tensor scale, c10::optional<torch::Tensor> workspace,
+                  int64_t nsk, int64_t nf,
+                  c10::optional<torch::Tensor> residual,
+                  c10::optional<torch::Tensor> norm_weight, double eps,
+                  c10::optional<torch::Tensor> out) {
+    gemm_quant_m256(
+        "gemm_w8_m256", check_w8,
+        [](void* y, float* ws, const void* x, const void* q, const void* s,
+           auto... rest) {
+            return launch_gemm_w8_m256(y, ws, x, q, (const float*)s, rest...);
+        },
+        y, x, q_frag, scale, workspace, nsk, nf, residual, norm_weight, eps, out);
 }
 
 void dequant_w8(torch::Tensor out, torch::Tensor q_frag, torch::Tensor scale) {
@@ -554,26 +573,8 @@ void gemm_w4_m256(torch::Tensor y, torch::Tensor x, torch::Tensor q_frag,
                   c10::optional<torch::Tensor> residual,
                   c10::optional<torch::Tensor> norm_weight, double eps,
                   c10::optional<torch::Tensor> out) {
-    check_bf16(x, "x");
-    check_bf16(y, "y");
-    TORCH_CHECK(x.is_contiguous() && y.is_contiguous());
-    TORCH_CHECK(x.dim() == 2 && y.dim() == 2);
-    const int M = x.size(0), K = x.size(1);
-    TORCH_CHECK(M >= 1 && M <= 256, "gemm_w4_m256 covers 1 <= M <= 256");
-    const int N = check_w4(q_frag, s_frag, K);
-    TORCH_CHECK(y.size(0) == M && y.size(1) == N);
-    TORCH_CHECK(nf == 4 || nf == 8, "nf must be 4 or 8");
-    TORCH_CHECK(N % (16 * nf) == 0, "N must be a multiple of 16*nf");
-    // nsk may exceed K/64: a slice without k-tiles writes zeros
-    TORCH_CHECK(nsk >= 1 && nsk <= 64, "nsk must be in [1, 64]");
-    float* ws = workspace_ptr(workspace, nsk * (int64_t)M * N);
-    TORCH_CHECK(nsk == 1 || ws != nullptr, "split-K needs a workspace");
-    const NormTail t = norm_tail(residual, norm_weight, out, M, N, nsk, ws);
-    CHECK_HIP(launch_gemm_w4_m256(y.data_ptr(), ws, x.data_ptr(),
-                                  q_frag.data_ptr(), s_frag.data_ptr(), M, N,
-                                  K, (int)nsk, (int)nf, t.residual,
-                                  t.norm_weight, (float)eps, t.out,
-                                  current_stream()));
+    gemm_quant_m256("gemm_w4_m256", check_w4, launch_gemm_w4_m256, y, x, q_frag,
+                    s_frag, workspace, nsk, nf, residual, norm_weight, eps, out);
 }
 
 void dequant_w4(torch::Tensor out, torch::Tensor q_frag, torch::Tensor s_frag) {

@@ -32,17 +32,9 @@
 // shapes (models/llama.py builds the fragment-major twins); prefill and
 // lm_head remain on the TunableOp-tuned library.
 
-#include "common.h"
-#include "gemm_launch.h"
-
-#define GM_BK 64  // k-depth of one staged tile (2 MFMA k-steps)
-
-typedef __attribute__((__vector_size__(8 * sizeof(short)))) short bf16x8;
-typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4;
-
-__device__ __forceinline__ f32x4 gm_mfma(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
+// GM_BK, the fragment types, gm_mfma / gm_cfence and the epilogue come from
+// gemm_macro.h, which also holds the register-staged variant's pipeline.
+#include "gemm_macro.h"
 
 // async 16-B-per-lane global->LDS copy. The LDS destination is
 // wave-uniform base + lane*16 (hardware rule); the global source is
@@ -59,15 +51,6 @@ __device__ __forceinline__ void gm_glds16(const void* g, char* smem, int ldsoff)
 template <int N>
 __device__ __forceinline__ void gm_vmwait() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// compiler-only memory fence: keeps LDS reads/DMA issues from being
-// scheduled across a raw s_barrier (the builtin is convergent but not a
-// compiler memory barrier)
-__device__ __forceinline__ void gm_cfence() { asm volatile("" ::: "memory"); }
-
-__device__ __forceinline__ float gm_silu(float g) {
-    return g / (1.f + __expf(-g));
 }
 
 // counted wait for "ahead" tiles of GPW glds each still in flight
@@ -221,57 +204,16 @@ __global__ void gemm_m256_kernel(
     }
 #undef GM_STAGE
 
-    // ---- epilogue: C fragment row = 4*(lane>>4) + r, col = lane&15 ----
-    const int m_base = wave * 32;
-    if (SPLITK) {
-        float* slab = yw + (size_t)blockIdx.y * M * N;
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m_base + f * 16 + (lane >> 4) * 4 + r;
-                if (row >= M) continue;
-#pragma unroll
-                for (int n = 0; n < NF; ++n)
-                    slab[(size_t)row * N + n0 + n * 16 + (lane & 15)] =
-                        acc[f][n][r];
-            }
-    } else if constexpr (SWIGLU) {
-        // block-16 interleaved gate/up twin (ops.interleave_gate_up):
-        // even fragment n holds the GATE columns, fragment n+1 the UP
-        // columns of the SAME 16 output columns — the pair lands in the
-        // same lane, so silu(g)*u needs no cross-lane traffic and the
-        // [M, N] intermediate + separate swiglu kernel disappear.
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m_base + f * 16 + (lane >> 4) * 4 + r;
-                if (row >= M) continue;
-#pragma unroll
-                for (int n = 0; n < NF; n += 2)
-                    y[(size_t)row * (N >> 1) + (n0 >> 1) + (n >> 1) * 16 +
-                      (lane & 15)] =
-                        f2bf(gm_silu(acc[f][n][r]) * acc[f][n + 1][r]);
-            }
-    } else {
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m_base + f * 16 + (lane >> 4) * 4 + r;
-                if (row >= M) continue;
-#pragma unroll
-                for (int n = 0; n < NF; ++n)
-                    y[(size_t)row * N + n0 + n * 16 + (lane & 15)] =
-                        f2bf(acc[f][n][r]);
-            }
-    }
+    // the fused swiglu store removes the [M, N] intermediate + separate
+    // swiglu kernel
+    gm_epilogue<NF, SPLITK, SWIGLU, false>(acc, y, yw, nullptr, M, N, n0, wave,
+                                           lane);
 }
 
 // ---------------------------------------------------------------------------
 // Register-staged variant (T14: global->reg loads issued one tile ahead,
-// ds_write AFTER the barrier, plain k-loop, 2 LDS buffers).
+// ds_write AFTER the barrier, plain k-loop, 2 LDS buffers): the pipeline of
+// gemm_macro.h with the bf16 W policy below.
 //
 // Why it exists: the all-glds variant above is capped by the LDS-DMA
 // landing cadence (~25-40 GB/s per CU; MI355X_MICROARCH.md "ldsdma-fill"),
@@ -285,182 +227,39 @@ __global__ void gemm_m256_kernel(
 // contiguous store groups.
 // ---------------------------------------------------------------------------
 
+// Fragment-major bf16 twin [K/32][N/16][64][8]: a unit is one 1-KiB
+// fragment, 16 B per lane, already in its LDS form. Unit u of a k64 tile
+// is k32 half u/NF, n-fragment u%NF, so it lands at u*1024 of the W area.
 // NTW: stream W through non-temporal loads — the weight stream has zero
 // reuse, so keeping it out of L2 leaves the cache to X and the consumers.
-template <int MW, int NF, bool SPLITK, bool SWIGLU = false, bool NTW = false>
-__launch_bounds__(MW * WAVE_SIZE)
-__global__ void gemm_m256r_kernel(
-    bf16* __restrict__ y, float* __restrict__ yw,
-    const bf16* __restrict__ x,  // [M, K]
-    const bf16* __restrict__ w,  // fragment-major [K/32][N/16][64][8]
-    int M, int N, int K, int nsk) {
-    static_assert(!(SWIGLU && SPLITK), "fused swiglu epilogue needs nsk=1");
-    static_assert(!SWIGLU || NF % 2 == 0, "fused swiglu pairs fragments");
-    constexpr int BM = MW * 32;
-    constexpr int BN = NF * 16;
-    constexpr int XB = BM * GM_BK * 2;
-    constexpr int WB = GM_BK * BN * 2;
-    constexpr int BUFB = XB + WB;
-    constexpr int XG_W = 4;                       // 1-KiB x units per wave
-    constexpr int WG_W = (2 * NF + MW - 1) / MW;  // 1-KiB w units per wave
-    static_assert((2 * NF) % MW == 0, "W frag split uneven across waves");
+template <int NF_, bool NTW>
+struct WBf16Frag {
+    static constexpr int NF = NF_;
+    static constexpr int UNITS = 2 * NF_;
+    static constexpr bool SCALED = false;
+    static constexpr bool SWIGLU = true;
+    typedef bf16x8 Regs;
 
-    __shared__ __attribute__((aligned(16))) char smem[2 * BUFB];
+    const bf16* src;
+    int n16;
 
-    const int lane = threadIdx.x & (WAVE_SIZE - 1);
-    const int wave = threadIdx.x >> 6;
-    const int n0 = blockIdx.x * BN;
-    const int n16 = N / 16;
-
-    const int ktiles = K / GM_BK;
-    const int kt_per = SPLITK ? (ktiles + nsk - 1) / nsk : ktiles;
-    const int kt0 = SPLITK ? blockIdx.y * kt_per : 0;
-    const int ntiles = min(ktiles - kt0, kt_per) > 0 ? min(ktiles - kt0, kt_per) : 0;
-
-    // X staging: unit i = rows [32w+8i, +8); lane -> row base+l/8, chunk
-    // l%8. Loads are linear (full 128-B lines); the XOR goes on the
-    // ds_write address. Per-unit row clamp for M < BM tails.
-    const int xrow = wave * 32 + (lane >> 3);
-    const bf16* xsrc[XG_W];
-#pragma unroll
-    for (int i = 0; i < XG_W; ++i) {
-        const int r = xrow + i * 8;
-        xsrc[i] = x + (size_t)(r < M ? r : 0) * K + (lane & 7) * 8;
+    __device__ __forceinline__ void init(const void* w, const void*, int N,
+                                         int n0, int lane) {
+        src = (const bf16*)w + (size_t)(n0 / 16) * 512 + lane * 8;
+        n16 = N / 16;
     }
-    // ds_write byte offset (swizzled) per unit: row*128 + (c ^ row&7)*16
-    const int xwoff = (xrow & (BM - 1)) * 128 + (((lane & 7) ^ (xrow & 7)) << 4);
-
-    int wfi[WG_W];
-#pragma unroll
-    for (int j = 0; j < WG_W; ++j) wfi[j] = wave + j * MW;
-
-    f32x4 acc[2][NF];
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-        for (int n = 0; n < NF; ++n) acc[f][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    bf16x8 xr[XG_W], wr[WG_W];  // one in-flight staging tile
-
-#define GMR_LOAD(T)                                                            \
-    do {                                                                       \
-        const int kt__ = kt0 + (T);                                            \
-        _Pragma("unroll") for (int i = 0; i < XG_W; ++i) xr[i] =               \
-            *(const __attribute__((address_space(1))) bf16x8*)(                \
-                xsrc[i] + (size_t)(kt__)*GM_BK);                               \
-        _Pragma("unroll") for (int j = 0; j < WG_W; ++j) {                     \
-            const size_t gfi__ = (size_t)(2 * kt__ + wfi[j] / NF) * n16 +      \
-                                 n0 / 16 + wfi[j] % NF;                        \
-            const __attribute__((address_space(1))) bf16x8* wp__ =             \
-                (const __attribute__((address_space(1))) bf16x8*)(             \
-                    w + gfi__ * 512 + lane * 8);                               \
-            wr[j] = NTW ? __builtin_nontemporal_load(wp__) : *wp__;            \
-        }                                                                      \
-    } while (0)
-#define GMR_WRITE(T)                                                           \
-    do {                                                                       \
-        char* buf__ = smem + ((T)&1) * BUFB;                                   \
-        _Pragma("unroll") for (int i = 0; i < XG_W; ++i)                       \
-            *(__attribute__((address_space(3))) bf16x8*)(                      \
-                (__attribute__((address_space(3))) char*)buf__ + xwoff +       \
-                i * 8 * 128) = xr[i];                                          \
-        _Pragma("unroll") for (int j = 0; j < WG_W; ++j)                       \
-            *(__attribute__((address_space(3))) bf16x8*)(                      \
-                (__attribute__((address_space(3))) char*)buf__ + XB +          \
-                wfi[j] * 1024 + lane * 16) = wr[j];                            \
-    } while (0)
-
-    const int arow0 = wave * 32 + (lane & 15);
-    const int alk = lane >> 4;
-
-    if (ntiles > 0) {
-        GMR_LOAD(0);
-        GMR_WRITE(0);
-        if (ntiles > 1) GMR_LOAD(1);  // in flight during compute(0)
-        gm_cfence();
-        __builtin_amdgcn_s_barrier();
-        gm_cfence();
-        for (int t = 0; t < ntiles; ++t) {
-            if (t + 1 < ntiles) {
-                // regs hold tile t+1 (issued last iter): write after the
-                // barrier, then immediately re-issue for tile t+2 so the
-                // loads overlap compute(t)
-                GMR_WRITE(t + 1);
-                if (t + 2 < ntiles) GMR_LOAD(t + 2);
-            }
-            const char* buf = smem + (t & 1) * BUFB;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                bf16x8 a[2], b[NF];
-#pragma unroll
-                for (int f = 0; f < 2; ++f) {
-                    const int row = arow0 + f * 16;
-                    const int chunk = (ks * 4 + alk) ^ (row & 7);
-                    a[f] = *(const __attribute__((address_space(3))) bf16x8*)(
-                        (const __attribute__((address_space(3))) char*)buf +
-                        (row & (BM - 1)) * 128 + chunk * 16);
-                }
-#pragma unroll
-                for (int n = 0; n < NF; ++n)
-                    b[n] = *(const __attribute__((address_space(3))) bf16x8*)(
-                        (const __attribute__((address_space(3))) char*)buf +
-                        XB + (ks * NF + n) * 1024 + lane * 16);
-#pragma unroll
-                for (int n = 0; n < NF; ++n)
-#pragma unroll
-                    for (int f = 0; f < 2; ++f)
-                        acc[f][n] = gm_mfma(a[f], b[n], acc[f][n]);
-            }
-            gm_cfence();
-            __builtin_amdgcn_s_barrier();
-            gm_cfence();
-        }
+    __device__ __forceinline__ void load(Regs& r, int unit, int kt) const {
+        const size_t gfi = (size_t)(2 * kt + unit / NF) * n16 + unit % NF;
+        const GM_GLOBAL bf16x8* p = (const GM_GLOBAL bf16x8*)(src + gfi * 512);
+        r = NTW ? __builtin_nontemporal_load(p) : *p;
     }
-#undef GMR_LOAD
-#undef GMR_WRITE
-
-    const int m_base = wave * 32;
-    if (SPLITK) {
-        float* slab = yw + (size_t)blockIdx.y * M * N;
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m_base + f * 16 + (lane >> 4) * 4 + r;
-                if (row >= M) continue;
-#pragma unroll
-                for (int n = 0; n < NF; ++n)
-                    slab[(size_t)row * N + n0 + n * 16 + (lane & 15)] =
-                        acc[f][n][r];
-            }
-    } else if constexpr (SWIGLU) {
-        // see gemm_m256_kernel's SWIGLU epilogue (block-16 interleaved twin)
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m_base + f * 16 + (lane >> 4) * 4 + r;
-                if (row >= M) continue;
-#pragma unroll
-                for (int n = 0; n < NF; n += 2)
-                    y[(size_t)row * (N >> 1) + (n0 >> 1) + (n >> 1) * 16 +
-                      (lane & 15)] =
-                        f2bf(gm_silu(acc[f][n][r]) * acc[f][n + 1][r]);
-            }
-    } else {
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m_base + f * 16 + (lane >> 4) * 4 + r;
-                if (row >= M) continue;
-#pragma unroll
-                for (int n = 0; n < NF; ++n)
-                    y[(size_t)row * N + n0 + n * 16 + (lane & 15)] =
-                        f2bf(acc[f][n][r]);
-            }
+    static __device__ __forceinline__ void write(GM_LDS char* wa, int unit,
+                                                 int lane, const Regs& r) {
+        *(GM_LDS bf16x8*)(wa + unit * 1024 + lane * 16) = r;
     }
-}
+};
+template <int NF> using WBf16FragLd = WBf16Frag<NF, false>;
+template <int NF> using WBf16FragNt = WBf16Frag<NF, true>;
 
 // ---------------------------------------------------------------------------
 // Producer/consumer variant (v2): wave-specialized for the W-stream-heavy
@@ -723,6 +522,14 @@ extern "C" hipError_t launch_gemm_m256(
         return launch_splitk_tail(y, workspace, M, N, nsk, residual,
                                   norm_weight, eps, norm_out, stream);
     }
+    if (variant == 1)
+        return pipe == 1
+                   ? launch_gemm_macro<WBf16FragNt>(
+                         y, workspace, x, w, nullptr, M, N, K, nsk, nf, swiglu,
+                         residual, norm_weight, eps, norm_out, stream)
+                   : launch_gemm_macro<WBf16FragLd>(
+                         y, workspace, x, w, nullptr, M, N, K, nsk, nf, swiglu,
+                         residual, norm_weight, eps, norm_out, stream);
     if (nf != 4 && nf != 8) return hipErrorInvalidValue;
     if ((N % (16 * nf)) != 0) return hipErrorInvalidValue;
     if (variant == 0) {
@@ -737,17 +544,7 @@ extern "C" hipError_t launch_gemm_m256(
     dim3 block(mw * WAVE_SIZE);
 #define GM_L2(MWV, NFV, SPLIT, SW)                                             \
     do {                                                                       \
-        if (variant == 1 && pipe == 1)                                         \
-            gemm_m256r_kernel<MWV, NFV, SPLIT, SW, true><<<grid, block, 0,     \
-                                                           stream>>>(         \
-                (bf16*)y, workspace, (const bf16*)x, (const bf16*)w, M, N, K,  \
-                nsk);                                                          \
-        else if (variant == 1)                                                 \
-            gemm_m256r_kernel<MWV, NFV, SPLIT, SW><<<grid, block, 0,           \
-                                                     stream>>>(               \
-                (bf16*)y, workspace, (const bf16*)x, (const bf16*)w, M, N, K,  \
-                nsk);                                                          \
-        else if (pipe == 1 && NFV == 4)                                        \
+        if (pipe == 1 && NFV == 4)                                             \
             gemm_m256_kernel<MWV, 4, 64, 4, SPLIT, SW><<<grid, block, 0,       \
                                                          stream>>>(           \
                 (bf16*)y, workspace, (const bf16*)x, (const bf16*)w, M, N, K,  \
