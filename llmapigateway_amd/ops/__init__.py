@@ -1405,6 +1405,10 @@ MOE_W4_RING_DEPTH = 4  # k groups; keep in sync with MW_D in moe_w4.hip
 # LLMAPI_MOE_BIG_MIN_ROWS=n (read at call time) overrides it. Measured in
 # profiles/r14_moe_prefill.md.
 MOE_BIG_MIN_ROWS = 128
+# The same threshold for MXFP4 experts (csrc/moe_w4_prefill.hip);
+# LLMAPI_MOE_W4_BIG_MIN_ROWS=n (read at call time) overrides it. None: the
+# route is off unless the knob is set. See profiles/r16_moe_w4_prefill.md.
+MOE_W4_BIG_MIN_ROWS: Optional[int] = None
 
 
 def moe_check_shapes(E: int, k: int, H: int, inter: int, weight_dtype: str = "auto") -> None:
@@ -1460,6 +1464,15 @@ def _moe_big_route(T: int, k: int, E: int, H: int, inter: int, quantised: bool) 
     return not quantised and moe_big_serves(H, inter) and T * k >= min_rows * E
 
 
+def _moe_big_w4_route(T: int, k: int, E: int, H: int, inter: int) -> bool:
+    """_moe_big_route for MXFP4 experts, from host integers only: a shape the
+    128-row tile serves and at least MOE_W4_BIG_MIN_ROWS pairs per expert on
+    average (never, while that is None and the knob is unset)."""
+    knob = os.environ.get("LLMAPI_MOE_W4_BIG_MIN_ROWS")
+    min_rows = int(knob) if knob else MOE_W4_BIG_MIN_ROWS
+    return min_rows is not None and moe_big_serves(H, inter) and T * k >= min_rows * E
+
+
 def moe_pack_weights(w: torch.Tensor, gate_up: bool) -> torch.Tensor:
     """[E, N, K] expert stack -> the resident GPU layout (on w's device)."""
     return reference.moe_pack_weights(w, gate_up)
@@ -1485,8 +1498,8 @@ def moe_route(x: torch.Tensor, w_router: torch.Tensor, k: int):
 
 def moe_align(ids: torch.Tensor, E: int, mf: Optional[int] = None) -> MoePlan:
     """GPU only: sort the pairs of ids [T, k] by expert. mf (1, 2, 4, or 8
-    for the prefill tile of bf16 experts) is the row-tile factor; by default
-    picked from the host integers T*k/E among 1, 2 and 4."""
+    for the 128-row prefill tile, bf16 or MXFP4 experts) is the row-tile
+    factor; by default picked from the host integers T*k/E among 1, 2 and 4."""
     T, k = ids.shape
     if mf is None:
         mf = _native().moe_pick_mf(T, k, E)
@@ -1580,8 +1593,9 @@ def moe_mlp(
     (route, align, gate_up+swiglu, down, combine+norm), none of which reads
     device data on the host. ids/weights given: the router is skipped.
     s_gate_up / s_down given (both or neither): MXFP4 expert weights, see
-    moe_gate_up_swiglu. A prefill batch of bf16 experts (_moe_big_route) runs
-    the two GEMMs on 128-row tiles, bit-identical to the 64-row ones."""
+    moe_gate_up_swiglu. A prefill batch (_moe_big_route for bf16 experts,
+    _moe_big_w4_route for MXFP4 ones) runs the two GEMMs on 128-row tiles,
+    bit-identical to the 64-row ones."""
     if (s_gate_up is None) != (s_down is None):
         raise ValueError("moe_mlp takes s_gate_up and s_down together")
     if not x.is_cuda:
@@ -1597,7 +1611,10 @@ def moe_mlp(
     if ids is None:
         ids, weights = moe_route(x, w_router, k)
     E, inter = w_gate_up.shape[0], w_gate_up.shape[2] * 8
-    big = _moe_big_route(x.shape[0], k, E, x.shape[1], inter, s_gate_up is not None)
+    if s_gate_up is not None:
+        big = _moe_big_w4_route(x.shape[0], k, E, x.shape[1], inter)
+    else:
+        big = _moe_big_route(x.shape[0], k, E, x.shape[1], inter, False)
     plan = moe_align(ids, E, 8 if big else None)
     act = moe_gate_up_swiglu(x, ids, w_gate_up, plan, s_gate_up=s_gate_up)
     y_pair = moe_down(act, ids, weights, w_down, plan, s_down=s_down)

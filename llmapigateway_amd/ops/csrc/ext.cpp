@@ -888,7 +888,7 @@ void moe_gemm_w4(torch::Tensor out, torch::Tensor a, torch::Tensor wq,
                 ws.device() == a.device(),
                 "wq / ws must be uint8 tensors on the device of a");
     TORCH_CHECK(epi == 0 || epi == 1, "epi must be 0 (swiglu) or 1 (down)");
-    TORCH_CHECK(mf == 1 || mf == 2 || mf == 4, "mf must be 1, 2 or 4");
+    TORCH_CHECK(mf == 1 || mf == 2 || mf == 4 || mf == 8, "mf must be 1, 2, 4 or 8");
     TORCH_CHECK(out.is_contiguous() && a.is_contiguous() && wq.is_contiguous() &&
                 ws.is_contiguous() && out.dim() == 2 && a.dim() == 2);
     TORCH_CHECK(wq.dim() == 5 && wq.size(3) == 64 && wq.size(4) == 16,
@@ -917,7 +917,8 @@ void moe_gemm_w4(torch::Tensor out, torch::Tensor a, torch::Tensor wq,
         TORCH_CHECK(a.size(0) == P / k, "x must be [T, H]");
         TORCH_CHECK(out.size(0) == cap && out.size(1) == N / 2, "act must be [cap, I]");
     } else {
-        TORCH_CHECK(N % 64 == 0, "hidden size must be a multiple of 64");
+        TORCH_CHECK(N % (mf == 8 ? 128 : 64) == 0, "hidden size must be a multiple of ",
+                    mf == 8 ? 128 : 64, " at mf = ", mf);
         TORCH_CHECK(a.size(0) == cap, "act must be [cap, I]");
         TORCH_CHECK(out.size(0) == P && out.size(1) == N, "y_pair must be [T*k, H]");
     }

@@ -237,8 +237,15 @@ hipError_t launch_w4_epi(int mf, dim3 grid, hipStream_t stream,
 
 }  // namespace
 
+// moe_w4_prefill.hip: the 128-row tile
+extern "C" hipError_t launch_moe_gemm_w4_big(
+    void* out, const void* a, const void* wq, const void* ws,
+    const int* sorted_pairs, const int* tile_expert, const float* rweights,
+    int epi, int max_tiles, int N, int K, int k, hipStream_t stream);
+
 // epi 0: act [cap, N/2] = swiglu(gather(x) · dequant(w[e])^T), N = 2I, K = H
 // epi 1: y_pair [P, N] = rweights · (act · dequant(w[e])^T),   N = H,  K = I
+// mf = 8 is moe_gemm_w4_big (moe_w4_prefill.hip): N % 128 == 0 for both
 extern "C" hipError_t launch_moe_gemm_w4(
     void* out, const void* a, const void* wq, const void* ws,
     const int* sorted_pairs, const int* tile_expert, const float* rweights,
@@ -246,6 +253,9 @@ extern "C" hipError_t launch_moe_gemm_w4(
     hipStream_t stream) {
     if (max_tiles <= 0 || k < 1 || K <= 0 || K % MW_GK != 0)
         return hipErrorInvalidValue;
+    if (mf == 8)
+        return launch_moe_gemm_w4_big(out, a, wq, ws, sorted_pairs, tile_expert,
+                                      rweights, epi, max_tiles, N, K, k, stream);
     if (epi == EPI_SWIGLU) {
         if (N <= 0 || N % 128 != 0) return hipErrorInvalidValue;
         return launch_w4_epi<EPI_SWIGLU>(

@@ -34,6 +34,7 @@ sources = [
     os.path.join(CSRC, "moe.hip"),
     os.path.join(CSRC, "moe_prefill.hip"),
     os.path.join(CSRC, "moe_w4.hip"),
+    os.path.join(CSRC, "moe_w4_prefill.hip"),
 ]
 
 setup(

@@ -21,7 +21,10 @@ alternating rounds.
 
 --weight-dtype=auto,mxfp4 also times moe_mlp on the MXFP4 quantisation of the
 same expert weights (csrc/moe_w4.hip) in the same alternating rounds and
-prints a second line per T.
+prints a second line per T. From 128 pairs per expert it is timed twice: with
+LLMAPI_MOE_W4_BIG_MIN_ROWS=128 on the 128-row MXFP4 tile
+(csrc/moe_w4_prefill.hip) and with the knob set high on the 64-row kernels
+("mxfp4 64-row / new").
 
 As in tools/lora_bench.py every route cycles through several layers' worth of
 weights (each layer's experts are 2.8 GB, far beyond the 256 MB L3), routes
@@ -148,6 +151,15 @@ def main():
                                1e-5, ids=ids, weights=wts,
                                s_gate_up=gu_w4[j][1], s_down=dn_w4[j][1])
 
+        def w4_knob(min_rows):
+            def run(i):
+                os.environ["LLMAPI_MOE_W4_BIG_MIN_ROWS"] = str(min_rows)
+                try:
+                    return moe_w4(i)
+                finally:
+                    del os.environ["LLMAPI_MOE_W4_BIG_MIN_ROWS"]
+            return run
+
         def dense(i):
             j = i % DENSE_LAYERS
             act = ops.swiglu_linear(x, d_gu[j], None, d_int[j])
@@ -181,8 +193,11 @@ def main():
         # windows of 0.1-0.3 s per round
         iters = 300 if T <= 256 else 100 if T <= 1024 else 40
         big = ops._moe_big_route(T, K, E, H, INTER, False)
+        big4 = w4 and ops.moe_big_serves(H, INTER) and T * K >= 128 * E
         m, a, b, *q = rounds(
-            [moe, dense, loop] + ([moe_old] if big else []) + ([moe_w4] if w4 else []),
+            [moe, dense, loop] + ([moe_old] if big else [])
+            + ([w4_knob(128 if big4 else 10**9)] if w4 else [])
+            + ([w4_knob(10**9)] if big4 else []),
             iters,
         )
         old = fmt(q.pop(0)) if big else "-"
@@ -194,14 +209,22 @@ def main():
             f"{m[0] / b[0]:.2f}, {used / m[0] / 1e3:.0f}, {fmt(al)}",
             flush=True,
         )
-        for t in q:
+        if q:
+            t = q[0]
             # disjoint: the two min-max ranges do not overlap
-            print(
-                f"  mxfp4: moe_mlp {fmt(t)} us, bf16/mxfp4 "
+            line = (
+                f"  mxfp4 (mf {8 if big4 else mf}): moe_mlp {fmt(t)} us, bf16/mxfp4 "
                 f"{m[0] / t[0]:.2f}, disjoint {t[2] < m[1] or m[2] < t[1]}, expert "
-                f"weight bytes / time {used * 4.25 / 16 / t[0] / 1e3:.0f} GB/s",
-                flush=True,
+                f"weight bytes / time {used * 4.25 / 16 / t[0] / 1e3:.0f} GB/s"
             )
+            if big4:
+                o = q[1]
+                line += (
+                    f", on the 64-row kernels {fmt(o)} us, mxfp4 64-row / new "
+                    f"{o[0] / t[0]:.2f}, new wholly below {t[2] < o[1]}, "
+                    f"mxfp4 new / (b) {t[0] / b[0]:.2f}"
+                )
+            print(line, flush=True)
 
 
 if __name__ == "__main__":
