@@ -63,6 +63,7 @@ class EngineSpec(BaseModel):
     kv_block_size: Optional[int] = None
     kv_dtype: str = "auto"               # "auto" (= compute dtype) | "fp8"
     weight_dtype: str = "auto"           # "auto" (= compute dtype) | "fp8" (e4m3 projections) | "mxfp4" (e2m1, block-32 scales)
+    expert_dtype: str = "auto"           # MoE expert stacks: "auto" (= weight_dtype) | "bf16" | "fp8" | "mxfp4"
     sliding_window: Optional[int] = None  # attention window; None = the preset's, 0 = off
     fail_rate: float = 0.0               # failure injection: P(request fails)
     fail_requests: Optional[int] = None  # failure injection: fail first N requests
@@ -114,6 +115,8 @@ class ProviderDetails(BaseModel):
                 updates["kv_dtype"] = q["kv_dtype"][0]
             if "weight_dtype" in q:
                 updates["weight_dtype"] = q["weight_dtype"][0]
+            if "expert_dtype" in q:
+                updates["expert_dtype"] = q["expert_dtype"][0]
             if "fail_rate" in q:
                 updates["fail_rate"] = float(q["fail_rate"][0])
             if updates:

@@ -34,7 +34,9 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..models.configs import ModelConfig, check_moe_supported, get_model_config
+from ..models.configs import (
+    ModelConfig, check_expert_dtype, check_moe_supported, get_model_config,
+)
 from ..models.llama import ForwardBatch, LlamaModel
 from .kvcache import PagedKVCache
 
@@ -182,6 +184,7 @@ class LLMEngine:
         admit_max_wait: Optional[float] = None,
         max_loras: int = 0,
         max_lora_rank: int = 16,
+        expert_dtype: str = "auto",
     ):
         if max_loras > 0 and tp_size > 1:
             raise NotImplementedError(
@@ -226,11 +229,16 @@ class LLMEngine:
             weight_dtype = os.environ.get("LLMAPI_WEIGHT_DTYPE", "auto")
         self.weight_dtype = weight_dtype  # "auto" (= compute dtype) | "fp8" | "mxfp4"
         check_moe_supported(full_config, tp_size, weight_dtype, max_loras)
+        # the expert stacks of a mixture-of-experts model: "auto" (follow
+        # weight_dtype) | "bf16" | "fp8" | "mxfp4", independent of qkv/o
+        check_expert_dtype(full_config, expert_dtype)
+        self.expert_dtype = expert_dtype
         self.model = LlamaModel(
             config, device=self.device, dtype=dtype, seed=seed,
             tp_group=tp_group, tp_rank=tp_rank, tp_size=tp_size,
             full_config=full_config, weight_dtype=weight_dtype,
             max_loras=max_loras, max_lora_rank=max_lora_rank,
+            expert_dtype=expert_dtype,
         )
         # multi-LoRA: name -> {"slot", "uid", "rank", "alpha"}; a slot is
         # rewritten only while no request refers to it

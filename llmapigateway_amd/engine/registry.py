@@ -134,6 +134,8 @@ class EngineRegistry:
             key += f"/kv{spec.kv_dtype}"
         if spec.weight_dtype not in ("auto", None):
             key += f"/w{spec.weight_dtype}"
+        if spec.expert_dtype not in ("auto", None):
+            key += f"/e{spec.expert_dtype}"
         if spec.sliding_window is not None:
             key += f"/sw{spec.sliding_window}"
         if spec.dtype not in ("bfloat16", None):
@@ -196,6 +198,7 @@ class EngineRegistry:
                     max_batch_size=spec.max_batch_size or self.settings.engine_max_batch_size,
                     kv_block_size=spec.kv_block_size or self.settings.engine_kv_block_size,
                     weight_dtype=spec.weight_dtype,
+                    expert_dtype=spec.expert_dtype,
                 )
                 handle = _TPGroupHandle(client, key)
                 self._engines[key] = handle
@@ -217,6 +220,7 @@ class EngineRegistry:
                 use_hipgraph=None if self.settings.engine_use_hipgraph else False,
                 kv_dtype=spec.kv_dtype,
                 weight_dtype=spec.weight_dtype,
+                expert_dtype=spec.expert_dtype,
                 sliding_window=spec.sliding_window,
                 max_loras=spec.max_loras,
                 max_lora_rank=spec.max_lora_rank,
@@ -748,6 +752,7 @@ class EngineRegistry:
                 "engine": key,
                 "model": eng.full_config.name,
                 "weight_dtype": getattr(eng, "weight_dtype", "auto"),
+                "expert_dtype": getattr(eng, "expert_dtype", "auto"),
                 **{k: int(v) for k, v in eng.stats.items()},
             }
             if hasattr(eng, "kv"):  # single-process engine

@@ -60,6 +60,7 @@ def _worker_main(
     inbox,
     outbox,
     weight_dtype: str = "auto",
+    expert_dtype: str = "auto",
 ) -> None:
     # fresh interpreter (spawn): do the heavy imports here
     import torch
@@ -94,6 +95,7 @@ def _worker_main(
             else False
         ),
         weight_dtype=weight_dtype,
+        expert_dtype=expert_dtype,
         tp_group=dist.group.WORLD,
         tp_rank=rank,
         tp_size=world,
@@ -246,16 +248,21 @@ class TPEngineClient:
         seed: int = 0,
         start_timeout: float = 600.0,
         weight_dtype: str = "auto",
+        expert_dtype: str = "auto",
     ):
-        from ..models.configs import check_moe_supported, get_model_config
+        from ..models.configs import (
+            check_expert_dtype, check_moe_supported, get_model_config,
+        )
         from .tokenizer import get_tokenizer
 
         self.full_config = get_model_config(model) if isinstance(model, str) else model
         check_moe_supported(self.full_config, tp, weight_dtype)  # before any worker starts
+        check_expert_dtype(self.full_config, expert_dtype)
         self.tokenizer = get_tokenizer("auto", self.full_config.vocab_size)
         self.max_model_len = max_model_len or self.full_config.max_positions
         self.tp = tp
         self.weight_dtype = weight_dtype
+        self.expert_dtype = expert_dtype
         ctx = mp.get_context("spawn")
         self.inbox = ctx.Queue()
         self.outbox = ctx.Queue()
@@ -266,7 +273,7 @@ class TPEngineClient:
                 args=(
                     r, tp, port, model, dtype, max_batch_size, kv_block_size,
                     num_blocks, self.max_model_len, seed, self.inbox, self.outbox,
-                    weight_dtype,
+                    weight_dtype, expert_dtype,
                 ),
                 daemon=True,
                 name=f"tp-worker-{r}",

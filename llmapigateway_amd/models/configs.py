@@ -216,7 +216,8 @@ def check_moe_supported(
             "mixture-of-experts models (num_experts > 0) are not supported "
             "with tensor parallelism (tp_size > 1) yet"
         )
-    # "mxfp4" is served (ops/csrc/moe_w4.hip); fp8 experts are not yet
+    # "mxfp4" is served (ops/csrc/moe_w4.hip). "fp8" is not: fp8 experts are
+    # served (ops/csrc/moe_w8.hip), but through expert_dtype="fp8" only
     if weight_dtype not in ("auto", "mxfp4"):
         raise NotImplementedError(
             "mixture-of-experts models (num_experts > 0) are not supported "
@@ -226,6 +227,25 @@ def check_moe_supported(
         raise NotImplementedError(
             "mixture-of-experts models (num_experts > 0) are not supported "
             "with LoRA adapters (max_loras > 0) yet"
+        )
+
+
+EXPERT_DTYPES = ("auto", "bf16", "fp8", "mxfp4")
+
+
+def check_expert_dtype(config: ModelConfig, expert_dtype: str = "auto") -> None:
+    """expert_dtype chooses the format of a mixture-of-experts config's
+    expert stacks: "auto" follows weight_dtype, the others are independent of
+    it. A dense config has no experts and takes "auto" only."""
+    if expert_dtype not in EXPERT_DTYPES:
+        raise ValueError(
+            f"expert_dtype must be one of {', '.join(map(repr, EXPERT_DTYPES))}, "
+            f"got {expert_dtype!r}"
+        )
+    if expert_dtype != "auto" and not config.num_experts:
+        raise ValueError(
+            f"expert_dtype={expert_dtype!r} needs a mixture-of-experts config "
+            f"(num_experts > 0); {config.name} is dense"
         )
 
 

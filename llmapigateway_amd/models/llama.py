@@ -49,7 +49,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from .. import ops
-from .configs import ModelConfig, check_moe_supported
+from .configs import ModelConfig, check_expert_dtype, check_moe_supported
 
 
 @dataclass
@@ -97,11 +97,13 @@ class LlamaModel:
         weight_dtype: str = "auto",
         max_loras: int = 0,
         max_lora_rank: int = 16,
+        expert_dtype: str = "auto",
     ):
         if weight_dtype not in ("auto", "fp8", "mxfp4"):
             raise ValueError(
                 f"weight_dtype must be 'auto', 'fp8' or 'mxfp4', got {weight_dtype!r}"
             )
+        check_expert_dtype(config, expert_dtype)
         # "fp8": the four projections of every layer are held as e4m3 bits
         # (fragment-major, ops.swizzle_weight_frag_fp8) plus one fp32 scale
         # per output channel, and run through ops.linear_w8; embeddings,
@@ -109,14 +111,23 @@ class LlamaModel:
         # "mxfp4": the same four as OCP MXFP4 — e2m1 nibbles plus one e8m0
         # scale per 32 k of a row (fragment-major,
         # ops.swizzle_weight_frag_mxfp4) — run through ops.linear_w4
-        # mixture of experts: not with TP, fp8 weights or adapters yet.
-        # "mxfp4" there: qkv/o as above, the router stays bf16, the expert
-        # stacks are MXFP4 panels run through ops.moe_mlp (ops/csrc/moe_w4.hip)
+        # mixture of experts: not with TP, weight_dtype="fp8" or adapters
+        # yet. qkv/o follow weight_dtype as above and the router stays bf16.
+        # The expert stacks follow expert_dtype: "auto" is weight_dtype's
+        # format, "bf16" / "fp8" / "mxfp4" choose it independently of the
+        # attention projections. fp8 stacks are e4m3 panels plus channel
+        # scales (ops/csrc/moe_w8.hip), MXFP4 ones nibble and scale panels
+        # (ops/csrc/moe_w4.hip), all run through ops.moe_mlp
         check_moe_supported(config, tp_size, weight_dtype, max_loras)
+        # the experts' format: "bf16", "fp8" or "mxfp4"; "auto" on a dense model
+        self.expert_dtype = expert_dtype
         if config.num_experts:
+            if expert_dtype == "auto":
+                self.expert_dtype = "mxfp4" if weight_dtype == "mxfp4" else "bf16"
             ops.moe_check_shapes(
                 config.num_experts, config.experts_per_token,
-                config.hidden_size, config.intermediate_size, weight_dtype,
+                config.hidden_size, config.intermediate_size,
+                "auto" if self.expert_dtype == "bf16" else self.expert_dtype,
             )
         self.weight_dtype = weight_dtype
         self.config = config
@@ -234,50 +245,53 @@ class LlamaModel:
         the stacks are held packed only (ops.moe_pack_weights: ONE resident
         copy, no twins); on the CPU they stay plain [E, 2I, H] / [E, H, I].
 
-        weight_dtype="mxfp4" draws the same weights in the same order, so the
-        model is the quantisation of the bf16 model of that seed: qkv and o
-        as in a dense layer, the router bf16, and every expert matrix
-        quantised as it is drawn (no bf16 stack ever exists) into
-        `experts_gate_up_q4/_s4` and `experts_down_q4/_s4`."""
+        Every format draws the same weights in the same order, so the model
+        is the quantisation of the bf16 model of that seed. weight_dtype
+        decides qkv and o as in a dense layer; the router stays bf16;
+        expert_dtype decides the stacks. A quantised stack is quantised
+        matrix by matrix as it is drawn (no bf16 stack ever exists): "mxfp4"
+        into `experts_gate_up_q4/_s4` and `experts_down_q4/_s4`, "fp8" (e4m3
+        bits and one fp32 scale per output channel) into
+        `experts_gate_up_q8/_s8` and `experts_down_q8/_s8`."""
         c = self.config
         E, hidden, inter = c.num_experts, c.hidden_size, c.intermediate_size
-        router = mk(E, hidden, std)
-        if self.weight_dtype == "mxfp4":
-            layer = {
-                "input_norm": torch.ones(hidden, dtype=self.dtype, device=self.device),
-                "post_norm": torch.ones(hidden, dtype=self.dtype, device=self.device),
-                "router": router,
-            }
-            for name, full in (("qkv", qkv), ("o", o)):
+        dev = self.device
+        layer = {
+            "input_norm": torch.ones(hidden, dtype=self.dtype, device=dev),
+            "post_norm": torch.ones(hidden, dtype=self.dtype, device=dev),
+            "router": mk(E, hidden, std),
+        }
+        for name, full in (("qkv", qkv), ("o", o)):
+            if self.weight_dtype == "mxfp4":
                 self._store_w4(layer, name, *ops.mxfp4_quantize_weight(full))
-            for name, rows, cols, w_std in (
-                ("experts_gate_up", 2 * inter, hidden, std),
-                ("experts_down", hidden, inter, out_std),
-            ):
-                q = torch.empty(E, rows, cols // 2, dtype=torch.uint8, device=self.device)
-                s = torch.empty(E, rows, cols // 32, dtype=torch.uint8, device=self.device)
+            else:
+                layer[name] = full
+        for name, rows, cols, w_std in (
+            ("experts_gate_up", 2 * inter, hidden, std),
+            ("experts_down", hidden, inter, out_std),
+        ):
+            gate_up = name == "experts_gate_up"
+            if self.expert_dtype == "mxfp4":
+                q = torch.empty(E, rows, cols // 2, dtype=torch.uint8, device=dev)
+                s = torch.empty(E, rows, cols // 32, dtype=torch.uint8, device=dev)
                 for e in range(E):
                     q[e], s[e] = ops.mxfp4_quantize_weight(mk(rows, cols, w_std))
                 self._store_experts_w4(layer, name, q, s)
-            return layer
-        gate_up = torch.empty(E, 2 * inter, hidden, dtype=self.dtype, device=self.device)
-        for e in range(E):
-            gate_up[e] = mk(2 * inter, hidden, std)
-        down = torch.empty(E, hidden, inter, dtype=self.dtype, device=self.device)
-        for e in range(E):
-            down[e] = mk(hidden, inter, out_std)
-        if self.device.type == "cuda":
-            gate_up = ops.moe_pack_weights(gate_up, True)
-            down = ops.moe_pack_weights(down, False)
-        return {
-            "input_norm": torch.ones(hidden, dtype=self.dtype, device=self.device),
-            "qkv": qkv,
-            "o": o,
-            "post_norm": torch.ones(hidden, dtype=self.dtype, device=self.device),
-            "router": router,
-            "experts_gate_up": gate_up,
-            "experts_down": down,
-        }
+            elif self.expert_dtype == "fp8":
+                q = torch.empty(E, rows, cols, dtype=torch.uint8, device=dev)
+                s = torch.empty(E, rows, dtype=torch.float32, device=dev)
+                for e in range(E):
+                    q[e], s[e] = ops.fp8_quantize_weight(mk(rows, cols, w_std))
+                # packed panels on the GPU, plain on the CPU
+                if dev.type == "cuda":
+                    q, s = ops.moe_pack_weights_fp8(q, s, gate_up)
+                layer[name + "_q8"], layer[name + "_s8"] = q, s
+            else:
+                w = torch.empty(E, rows, cols, dtype=self.dtype, device=dev)
+                for e in range(E):
+                    w[e] = mk(rows, cols, w_std)
+                layer[name] = ops.moe_pack_weights(w, gate_up) if dev.type == "cuda" else w
+        return layer
 
     def _quant_layer(self, qkv_full, o_full, gu_full, down_full) -> Dict[str, torch.Tensor]:
         """One layer's dict in a quantised mode, from the full (unsharded)
@@ -374,6 +388,8 @@ class LlamaModel:
         check_moe_supported(self.config, weight_dtype=mode)
         if self.weight_dtype != "auto":
             raise RuntimeError(f"weights are already {self.weight_dtype}")
+        if self.config.num_experts and self.expert_dtype != "bf16":
+            raise RuntimeError(f"expert weights are already {self.expert_dtype}")
         if self.tp_size > 1:
             # row shards would get per-shard scales: not the TP=1 model
             raise RuntimeError(
@@ -405,6 +421,8 @@ class LlamaModel:
             self._build_twins()
         else:
             self.weight_dtype = mode
+            if self.config.num_experts:
+                self.expert_dtype = mode
             self._reserve_w8_buffer()
         return self
 
@@ -805,13 +823,15 @@ class LlamaModel:
                 residual, layer["post_norm"],
             )
             if c.num_experts:
-                if self.weight_dtype == "mxfp4":
+                if self.expert_dtype != "bf16":
+                    # ops.moe_mlp tells fp8 from MXFP4 by the scales' dtype
+                    q, s = ("_q8", "_s8") if self.expert_dtype == "fp8" else ("_q4", "_s4")
                     x, residual = ops.moe_mlp(
-                        x, layer["router"], layer["experts_gate_up_q4"],
-                        layer["experts_down_q4"], c.experts_per_token, residual,
+                        x, layer["router"], layer["experts_gate_up" + q],
+                        layer["experts_down" + q], c.experts_per_token, residual,
                         next_norm, c.rms_eps,
-                        s_gate_up=layer["experts_gate_up_s4"],
-                        s_down=layer["experts_down_s4"],
+                        s_gate_up=layer["experts_gate_up" + s],
+                        s_down=layer["experts_down" + s],
                     )
                     continue
                 x, residual = ops.moe_mlp(

@@ -59,6 +59,10 @@ from .reference import (  # re-export (MXFP4 expert layout of csrc/moe_w4.hip)
     moe_pack_weights_mxfp4,
     moe_unpack_weights_mxfp4,
 )
+from .reference import (  # re-export (fp8 expert layout of csrc/moe_w8.hip)
+    moe_pack_weights_fp8,
+    moe_unpack_weights_fp8,
+)
 
 _C = None
 _C_ERR: Optional[str] = None
@@ -1400,6 +1404,10 @@ MOE_MAX_TOPK = 8
 MOE_MAX_HIDDEN = 8192  # moe_route: four x rows in 64 KiB of dynamic LDS
 MOE_W4_GROUP = reference.MOE_W4_GROUP  # k of one group of the MXFP4 expert layout
 MOE_W4_RING_DEPTH = 4  # k groups; keep in sync with MW_D in moe_w4.hip
+MOE_W8_GROUP = reference.MOE_W8_GROUP  # k of one group of the fp8 expert layout
+# k groups; keep in sync with MW8_D in moe_w8.hip. 2, 4, 6 and 8 were timed:
+# profiles/r17_moe_fp8.md
+MOE_W8_RING_DEPTH = 4
 # Pairs per expert on average (T*k / E) from which moe_mlp takes the 128-row
 # prefill tile (mf = 8, csrc/moe_prefill.hip) for bf16 experts;
 # LLMAPI_MOE_BIG_MIN_ROWS=n (read at call time) overrides it. Measured in
@@ -1412,8 +1420,10 @@ MOE_W4_BIG_MIN_ROWS: Optional[int] = None
 
 
 def moe_check_shapes(E: int, k: int, H: int, inter: int, weight_dtype: str = "auto") -> None:
-    """The shapes the MoE kernels serve; anything else is an error. MXFP4
-    expert weights are laid out in k groups of 128 (csrc/moe_w4.hip)."""
+    """The shapes the MoE kernels serve; anything else is an error.
+    weight_dtype is the experts' format: "auto" (bf16), "fp8" or "mxfp4".
+    MXFP4 expert weights are laid out in k groups of 128 (csrc/moe_w4.hip);
+    fp8 ones in k groups of 64 (csrc/moe_w8.hip), which adds no condition."""
     if not (2 <= E <= MOE_MAX_EXPERTS):
         raise ValueError(f"MoE needs 2 <= num_experts <= {MOE_MAX_EXPERTS}, got {E}")
     if not (1 <= k <= min(E, MOE_MAX_TOPK)):
@@ -1478,6 +1488,28 @@ def moe_pack_weights(w: torch.Tensor, gate_up: bool) -> torch.Tensor:
     return reference.moe_pack_weights(w, gate_up)
 
 
+def _moe_expert_format(scale: Optional[torch.Tensor]) -> str:
+    """The experts' format from the scale tensor that comes with them: none
+    is bf16, fp32 [E, N] channel scales are fp8, uint8 block scales MXFP4."""
+    if scale is None:
+        return "bf16"
+    if scale.dtype == torch.float32:
+        return "fp8"
+    if scale.dtype == torch.uint8:
+        return "mxfp4"
+    raise ValueError(
+        f"expert scales must be fp32 (fp8 experts) or uint8 (MXFP4 experts), "
+        f"got {scale.dtype}"
+    )
+
+
+def _moe_dequantize_experts(w: torch.Tensor, scale: torch.Tensor, dtype) -> torch.Tensor:
+    """The CPU route of quantised experts: plain stack -> [E, N, K]."""
+    if _moe_expert_format(scale) == "fp8":
+        return reference.moe_dequantize_experts_fp8(w, scale, dtype)
+    return reference.moe_dequantize_experts_mxfp4(w, scale, dtype)
+
+
 def moe_cap(P: int, E: int, mf: int) -> int:
     """Rows of the sorted order for P pairs in the worst case: every expert
     may pad up to BM - 1 rows; rounded up to whole tiles."""
@@ -1518,11 +1550,15 @@ def moe_gate_up_swiglu(
     """swiglu(x[t] @ w_gate_up[ids[t, j]].T) per pair. CPU: [T*k, I] in pair
     order. GPU: w_gate_up packed, act [plan.cap, I] in sorted order (padding
     rows are not written), into `out` when given. With s_gate_up the weights
-    are MXFP4: plain ([E, 2I, H/2], [E, 2I, H/32]) on the CPU, the panels of
-    moe_pack_weights_mxfp4 on the GPU (csrc/moe_w4.hip)."""
+    are quantised, and its dtype says how. uint8: MXFP4, plain ([E, 2I, H/2],
+    [E, 2I, H/32]) on the CPU, the panels of moe_pack_weights_mxfp4 on the
+    GPU (csrc/moe_w4.hip). fp32: fp8, plain (e4m3 bits [E, 2I, H], channel
+    scales [E, 2I]) on the CPU, the panels of moe_pack_weights_fp8 on the GPU
+    (csrc/moe_w8.hip; plan.mf 1, 2 or 4). Any other dtype is a ValueError."""
+    fmt = _moe_expert_format(s_gate_up)
     if not x.is_cuda:
         if s_gate_up is not None:
-            w_gate_up = reference.moe_dequantize_experts_mxfp4(w_gate_up, s_gate_up, x.dtype)
+            w_gate_up = _moe_dequantize_experts(w_gate_up, s_gate_up, x.dtype)
         return reference.moe_gate_up_swiglu(x, ids, w_gate_up)
     if plan is None:
         raise ValueError("moe_gate_up_swiglu on the GPU needs moe_align's plan")
@@ -1531,7 +1567,11 @@ def moe_gate_up_swiglu(
     act = out
     if act is None:
         act = torch.empty(plan.cap, inter, dtype=x.dtype, device=x.device)
-    if s_gate_up is not None:
+    if fmt == "fp8":
+        _native().moe_gemm_w8(act, x, w_gate_up, s_gate_up, plan.sorted_pairs,
+                              plan.tile_expert, None, 0, plan.mf, k, ids.numel())
+        return act
+    if fmt == "mxfp4":
         _native().moe_gemm_w4(act, x, w_gate_up, s_gate_up, plan.sorted_pairs,
                               plan.tile_expert, None, 0, plan.mf, k, ids.numel())
         return act
@@ -1547,11 +1587,12 @@ def moe_down(
 ) -> torch.Tensor:
     """y_pair [T*k, H] = weights[t, j] * (act row @ w_down[ids[t, j]].T) in
     pair order. GPU: act in the plan's sorted order, w_down packed; into
-    `out` when given. With s_down the weights are MXFP4, as in
-    moe_gate_up_swiglu."""
+    `out` when given. With s_down the weights are MXFP4 (uint8 scales) or
+    fp8 (fp32 scales [E, H]), as in moe_gate_up_swiglu."""
+    fmt = _moe_expert_format(s_down)
     if not act.is_cuda:
         if s_down is not None:
-            w_down = reference.moe_dequantize_experts_mxfp4(w_down, s_down, act.dtype)
+            w_down = _moe_dequantize_experts(w_down, s_down, act.dtype)
         return reference.moe_down(act, ids, weights, w_down)
     if plan is None:
         raise ValueError("moe_down on the GPU needs moe_align's plan")
@@ -1559,7 +1600,12 @@ def moe_down(
     if y_pair is None:
         y_pair = torch.empty(ids.numel(), w_down.shape[2] * 16, dtype=act.dtype,
                              device=act.device)
-    if s_down is not None:
+    if fmt == "fp8":
+        _native().moe_gemm_w8(y_pair, act, w_down, s_down, plan.sorted_pairs,
+                              plan.tile_expert, weights, 1, plan.mf,
+                              ids.shape[1], ids.numel())
+        return y_pair
+    if fmt == "mxfp4":
         _native().moe_gemm_w4(y_pair, act, w_down, s_down, plan.sorted_pairs,
                               plan.tile_expert, weights, 1, plan.mf,
                               ids.shape[1], ids.numel())
@@ -1592,16 +1638,21 @@ def moe_mlp(
     """The MoE layer tail -> (normed, residual): five launches on the GPU
     (route, align, gate_up+swiglu, down, combine+norm), none of which reads
     device data on the host. ids/weights given: the router is skipped.
-    s_gate_up / s_down given (both or neither): MXFP4 expert weights, see
+    s_gate_up / s_down given (both or neither, of one dtype): quantised
+    expert weights, uint8 scales for MXFP4 and fp32 ones for fp8, see
     moe_gate_up_swiglu. A prefill batch (_moe_big_route for bf16 experts,
     _moe_big_w4_route for MXFP4 ones) runs the two GEMMs on 128-row tiles,
-    bit-identical to the 64-row ones."""
+    bit-identical to the 64-row ones; fp8 experts always take moe_pick_mf's
+    tile."""
     if (s_gate_up is None) != (s_down is None):
         raise ValueError("moe_mlp takes s_gate_up and s_down together")
+    fmt = _moe_expert_format(s_gate_up)
+    if fmt != _moe_expert_format(s_down):
+        raise ValueError("moe_mlp takes s_gate_up and s_down of one dtype")
     if not x.is_cuda:
         if s_gate_up is not None:
-            w_gate_up = reference.moe_dequantize_experts_mxfp4(w_gate_up, s_gate_up, x.dtype)
-            w_down = reference.moe_dequantize_experts_mxfp4(w_down, s_down, x.dtype)
+            w_gate_up = _moe_dequantize_experts(w_gate_up, s_gate_up, x.dtype)
+            w_down = _moe_dequantize_experts(w_down, s_down, x.dtype)
         if ids is None:
             return reference.moe_mlp(x, w_router, w_gate_up, w_down, k, residual,
                                      norm_w, eps)
@@ -1611,7 +1662,9 @@ def moe_mlp(
     if ids is None:
         ids, weights = moe_route(x, w_router, k)
     E, inter = w_gate_up.shape[0], w_gate_up.shape[2] * 8
-    if s_gate_up is not None:
+    if fmt == "fp8":
+        big = False  # no 128-row fp8 tile
+    elif fmt == "mxfp4":
         big = _moe_big_w4_route(x.shape[0], k, E, x.shape[1], inter)
     else:
         big = _moe_big_route(x.shape[0], k, E, x.shape[1], inter, False)
@@ -1698,6 +1751,8 @@ __all__ = [
     "moe_unpack_weights",
     "moe_pack_weights_mxfp4",
     "moe_unpack_weights_mxfp4",
+    "moe_pack_weights_fp8",
+    "moe_unpack_weights_fp8",
     "moe_cap",
     "moe_big_serves",
     "moe_route",

@@ -36,6 +36,7 @@ hipError_t launch_moe_align(int*, int*, const int*, int, int, int, int, hipStrea
 hipError_t launch_moe_gemm(void*, const void*, const void*, const int*, const int*, const float*, int, int, int, int, int, int, hipStream_t);
 hipError_t launch_moe_combine_norm(void*, void*, const void*, const void*, float, int, int, int, hipStream_t);
 hipError_t launch_moe_gemm_w4(void*, const void*, const void*, const void*, const int*, const int*, const float*, int, int, int, int, int, int, hipStream_t);
+hipError_t launch_moe_gemm_w8(void*, const void*, const void*, const float*, const int*, const int*, const float*, int, int, int, int, int, int, hipStream_t);
 }
 
 namespace {
@@ -765,7 +766,7 @@ void lora_expand_seg(torch::Tensor y, torch::Tensor tpart, torch::Tensor B,
         (int)tpart.size(0), current_stream()));
 }
 
-// ---- mixture of experts (moe.hip, moe_prefill.hip, moe_w4.hip) ----
+// ---- mixture of experts (moe.hip, moe_prefill.hip, moe_w4.hip, moe_w8.hip) ----
 void check_moe_shape(int64_t E, int64_t k) {
     TORCH_CHECK(E >= 2 && E <= 64, "MoE kernels support 2 <= num_experts <= 64, got ", E);
     TORCH_CHECK(k >= 1 && k <= 8 && k <= E,
@@ -929,6 +930,63 @@ void moe_gemm_w4(torch::Tensor out, torch::Tensor a, torch::Tensor wq,
                                  current_stream()));
 }
 
+// moe_gemm with fp8 expert weights (ops.moe_pack_weights_fp8): wq
+// [E, K/64, N/16, 64, 16] e4m3 bytes, scale [E, N] fp32 (one per output
+// channel, in the row order of wq). mf is 1, 2 or 4: there is no 128-row tile
+void moe_gemm_w8(torch::Tensor out, torch::Tensor a, torch::Tensor wq,
+                 torch::Tensor scale, torch::Tensor sorted_pairs,
+                 torch::Tensor tile_expert,
+                 c10::optional<torch::Tensor> rweights, int64_t epi, int64_t mf,
+                 int64_t k, int64_t P) {
+    check_bf16(out, "out");
+    check_bf16(a, "a");
+    check_i32(sorted_pairs, "sorted_pairs");
+    check_i32(tile_expert, "tile_expert");
+    TORCH_CHECK(wq.is_cuda() && scale.is_cuda() && wq.scalar_type() == torch::kUInt8 &&
+                scale.scalar_type() == torch::kFloat32 && wq.device() == a.device() &&
+                scale.device() == a.device(),
+                "wq must be a uint8 and scale an fp32 tensor on the device of a");
+    TORCH_CHECK(epi == 0 || epi == 1, "epi must be 0 (swiglu) or 1 (down)");
+    TORCH_CHECK(mf == 1 || mf == 2 || mf == 4, "mf must be 1, 2 or 4 with fp8 experts");
+    TORCH_CHECK(out.is_contiguous() && a.is_contiguous() && wq.is_contiguous() &&
+                scale.is_contiguous() && out.dim() == 2 && a.dim() == 2);
+    TORCH_CHECK(wq.dim() == 5 && wq.size(3) == 64 && wq.size(4) == 16,
+                "wq must be packed [E, K/64, N/16, 64, 16] (ops.moe_pack_weights_fp8)");
+    const int64_t E = wq.size(0), K = wq.size(1) * 64, N = wq.size(2) * 16;
+    TORCH_CHECK(scale.dim() == 2 && scale.size(0) == E && scale.size(1) == N,
+                "scale must be [E, N] for the E, N of wq");
+    const int64_t BM = 16 * mf, tiles = tile_expert.numel(), cap = tiles * BM;
+    check_moe_shape(E, k);
+    TORCH_CHECK(sorted_pairs.numel() == cap, "sorted_pairs must be [cap]");
+    TORCH_CHECK(a.size(1) == K, "a must be [rows, K]");
+    // P = T * k pairs; only the down epilogue reads the routing weights
+    const float* rw = nullptr;
+    if (epi == 1) {
+        TORCH_CHECK(rweights.has_value() && rweights->is_cuda() &&
+                    rweights->scalar_type() == torch::kFloat32 &&
+                    rweights->is_contiguous() && rweights->numel() == P,
+                    "weights must be fp32 [T, k]");
+        rw = rweights->data_ptr<float>();
+    }
+    TORCH_CHECK(P > 0 && P % k == 0 && cap >= P + E * (BM - 1),
+                "cap too small for the pairs");
+    if (epi == 0) {
+        TORCH_CHECK(N % 128 == 0, "intermediate size must be a multiple of 64");
+        TORCH_CHECK(a.size(0) == P / k, "x must be [T, H]");
+        TORCH_CHECK(out.size(0) == cap && out.size(1) == N / 2, "act must be [cap, I]");
+    } else {
+        TORCH_CHECK(N % 64 == 0, "hidden size must be a multiple of 64");
+        TORCH_CHECK(a.size(0) == cap, "act must be [cap, I]");
+        TORCH_CHECK(out.size(0) == P && out.size(1) == N, "y_pair must be [T*k, H]");
+    }
+    CHECK_HIP(launch_moe_gemm_w8(out.data_ptr(), a.data_ptr(), wq.data_ptr(),
+                                 scale.data_ptr<float>(),
+                                 sorted_pairs.data_ptr<int>(),
+                                 tile_expert.data_ptr<int>(), rw, (int)epi,
+                                 (int)mf, (int)tiles, (int)N, (int)K, (int)k,
+                                 current_stream()));
+}
+
 void moe_combine_norm(torch::Tensor normed, torch::Tensor residual,
                       torch::Tensor y_pair, torch::Tensor norm_w, double eps,
                       int64_t k) {
@@ -958,6 +1016,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("moe_gemm", &moe_gemm, "grouped expert GEMM (epi 0: gate_up+swiglu, 1: down)");
     m.def("moe_gemm_w4", &moe_gemm_w4,
           "grouped expert GEMM with MXFP4 expert weights (W4A16)");
+    m.def("moe_gemm_w8", &moe_gemm_w8,
+          "grouped expert GEMM with fp8 expert weights (W8A16)");
     m.def("moe_combine_norm", &moe_combine_norm,
           "sum of a token's k expert rows + residual add + RMSNorm");
     m.def("lora_shrink", &lora_shrink,

@@ -514,6 +514,65 @@ def moe_dequantize_experts_mxfp4(
     )
 
 
+MOE_W8_GROUP = 64  # k of one group of the fp8 expert layout
+
+
+def moe_pack_weights_fp8(q: torch.Tensor, scale: torch.Tensor, gate_up: bool):
+    """fp8 expert stack (bits uint8 [E, N, K], scale fp32 [E, N], every
+    expert as fp8_quantize_weight writes it) -> the resident GPU layout of
+    csrc/moe_w8.hip, k grouped by 64:
+
+    q_panel [E, K/64, N/16, 64, 16]: swizzle_weight_frag_fp8 per expert —
+        [e][g][n16][lane][h*8 + i] = q[e][n16*16 + (lane & 15)][g*64 + h*32 +
+        (lane >> 4)*8 + i], the lane's share of the mfma_f32_16x16x32_bf16 B
+        fragments of the two k32 steps of the group; one 16-byte load per
+        lane and group.
+    s_panel [E, N]: the channel scales in the row order of q_panel.
+
+    gate_up=True first permutes the rows of bits and scales alike to the
+    block-16 gate/up interleave of moe_pack_weights."""
+    E, N, K = q.shape
+    if N % 64 or K % MOE_W8_GROUP:
+        raise ValueError(f"expert weights need N, K in multiples of 64, got {(N, K)}")
+    if scale.shape != (E, N):
+        raise ValueError(f"scale must be [E, N], got {tuple(scale.shape)}")
+    if gate_up:
+        q = q.view(E, 2, N // 32, 16, K).transpose(1, 2).reshape(E, N, K)
+        scale = scale.view(E, 2, N // 32, 16).transpose(1, 2).reshape(E, N)
+    # k = g*64 + h*32 + c*8 + i, n = n16*16 + r; lane = c*16 + r, byte = h*8 + i
+    q_panel = (
+        q.view(E, N // 16, 16, K // 64, 2, 4, 8)
+        .permute(0, 3, 1, 5, 2, 4, 6)
+        .reshape(E, K // 64, N // 16, 64, 16)
+        .contiguous()
+    )
+    return q_panel, scale.float().contiguous()
+
+
+def moe_unpack_weights_fp8(q_panel: torch.Tensor, s_panel: torch.Tensor, gate_up: bool):
+    """Inverse of moe_pack_weights_fp8: -> (bits [E, N, K], scale [E, N])."""
+    E, G, n16 = q_panel.shape[:3]
+    N, K = n16 * 16, G * MOE_W8_GROUP
+    q = (
+        q_panel.view(E, G, n16, 4, 16, 2, 8)
+        .permute(0, 2, 4, 1, 5, 3, 6)
+        .reshape(E, N, K)
+    )
+    scale = s_panel
+    if gate_up:
+        q = q.view(E, N // 32, 2, 16, K).transpose(1, 2).reshape(E, N, K)
+        scale = scale.view(E, N // 32, 2, 16).transpose(1, 2).reshape(E, N)
+    return q.contiguous(), scale.contiguous()
+
+
+def moe_dequantize_experts_fp8(
+    q: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype = torch.bfloat16
+) -> torch.Tensor:
+    """fp8 expert stack (bits [E, N, K], scale [E, N]) -> [E, N, K]; exact
+    for bf16 and wider, as fp8_dequantize_weight."""
+    return (q.view(torch.float8_e4m3fn).float() * scale.float().unsqueeze(-1)).to(dtype)
+
+
 def kv_cache_write(
     k: torch.Tensor,
     v: torch.Tensor,

@@ -35,6 +35,7 @@ sources = [
     os.path.join(CSRC, "moe_prefill.hip"),
     os.path.join(CSRC, "moe_w4.hip"),
     os.path.join(CSRC, "moe_w4_prefill.hip"),
+    os.path.join(CSRC, "moe_w8.hip"),
 ]
 
 setup(

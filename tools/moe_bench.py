@@ -26,12 +26,16 @@ LLMAPI_MOE_W4_BIG_MIN_ROWS=128 on the 128-row MXFP4 tile
 (csrc/moe_w4_prefill.hip) and with the knob set high on the 64-row kernels
 ("mxfp4 64-row / new").
 
+--weight-dtype=auto,fp8 (or auto,mxfp4,fp8) likewise times moe_mlp on the fp8
+quantisation of the same expert weights (csrc/moe_w8.hip; moe_pick_mf's tile
+at every T, there is no 128-row fp8 tile) and prints a line per T.
+
 As in tools/lora_bench.py every route cycles through several layers' worth of
 weights (each layer's experts are 2.8 GB, far beyond the 256 MB L3), routes
 alternate, three rounds each; the median round is reported with the min-max
 of the three. Run on the GPU box:
 
-    python tools/moe_bench.py [--ts=16,64,256,512,1024,2048,4096] [--weight-dtype=auto,mxfp4]
+    python tools/moe_bench.py [--ts=16,64,256,512,1024,2048,4096] [--weight-dtype=auto,mxfp4,fp8]
 """
 
 import os
@@ -88,7 +92,7 @@ def main():
             dtypes = tuple(a[15:].split(","))
         else:
             raise SystemExit(f"unknown argument {a}")
-    assert set(dtypes) <= {"auto", "mxfp4"} and "auto" in dtypes, dtypes
+    assert set(dtypes) <= {"auto", "mxfp4", "fp8"} and "auto" in dtypes, dtypes
 
     def rand(*shape):
         return (torch.randn(*shape, device=dev) * 0.02).bfloat16()
@@ -106,6 +110,15 @@ def main():
             torch.stack([q for q, _ in qs]), torch.stack([s for _, s in qs]), gate_up
         )
 
+    def pack_w8(w, gate_up):
+        qs = [ops.fp8_quantize_weight(w[e]) for e in range(E)]
+        return ops.moe_pack_weights_fp8(
+            torch.stack([q for q, _ in qs]), torch.stack([s for _, s in qs]), gate_up
+        )
+
+    w8 = "fp8" in dtypes
+    gu_w8 = [pack_w8(w, True) for w in gu_plain] if w8 else []
+    dn_w8 = [pack_w8(w, False) for w in dn_plain] if w8 else []
     w4 = "mxfp4" in dtypes
     gu_w4 = [pack_w4(w, True) for w in gu_plain] if w4 else []
     dn_w4 = [pack_w4(w, False) for w in dn_plain] if w4 else []
@@ -150,6 +163,12 @@ def main():
             return ops.moe_mlp(x, router, gu_w4[j][0], dn_w4[j][0], K, res, norm_w,
                                1e-5, ids=ids, weights=wts,
                                s_gate_up=gu_w4[j][1], s_down=dn_w4[j][1])
+
+        def moe_w8(i):
+            j = i % MOE_LAYERS
+            return ops.moe_mlp(x, router, gu_w8[j][0], dn_w8[j][0], K, res, norm_w,
+                               1e-5, ids=ids, weights=wts,
+                               s_gate_up=gu_w8[j][1], s_down=dn_w8[j][1])
 
         def w4_knob(min_rows):
             def run(i):
@@ -197,10 +216,12 @@ def main():
         m, a, b, *q = rounds(
             [moe, dense, loop] + ([moe_old] if big else [])
             + ([w4_knob(128 if big4 else 10**9)] if w4 else [])
-            + ([w4_knob(10**9)] if big4 else []),
+            + ([w4_knob(10**9)] if big4 else [])
+            + ([moe_w8] if w8 else []),
             iters,
         )
         old = fmt(q.pop(0)) if big else "-"
+        t8 = q.pop() if w8 else None
         (al,) = rounds([align], 300)
         used = len(torch.unique(ids)) * 3 * H * INTER * 2  # bytes of experts hit
         mf = 8 if big else ops._native().moe_pick_mf(T, K, E)
@@ -224,6 +245,15 @@ def main():
                     f"{o[0] / t[0]:.2f}, new wholly below {t[2] < o[1]}, "
                     f"mxfp4 new / (b) {t[0] / b[0]:.2f}"
                 )
+            print(line, flush=True)
+        if t8:
+            line = (
+                f"  fp8 (mf {ops._native().moe_pick_mf(T, K, E)}): moe_mlp {fmt(t8)} us, "
+                f"bf16/fp8 {m[0] / t8[0]:.2f}, disjoint {t8[2] < m[1] or m[2] < t8[1]}, "
+                f"expert weight bytes / time {used / 2 / t8[0] / 1e3:.0f} GB/s"
+            )
+            if q:
+                line += f", mxfp4/fp8 {q[0][0] / t8[0]:.2f}"
             print(line, flush=True)
 
 
